@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: Chebyshev recurrence steps/s on the 4N x 4N BdG Hamiltonian.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up the headline matrix, warms up, times the K steps and prints one JSON line;
+`--dump-outputs DIR` also writes what the timed call returned (DIR/moments.npy, DIR/free_energy.npy,
+float64; the inputs are seeded, so two runs with the same arguments get the same inputs).  Everything
+else below - the CPU baseline, the comparison passes on other kernels and matrices, the wall times
+through the Python API - runs only with `--full`; without it those entries of the line are null.
 
 Workload (BASELINE.json configs[2], the configuration the roofline target is
 quoted on): CubicLattice((1000,1000,1)), H_ii = 3σ0 - 0.05σ3, Δ_ii = -0.1 iσ2,
@@ -381,9 +387,10 @@ def main():
     ap.add_argument("--vectors-per-gpu", type=int, default=8)
     ap.add_argument("--vector-kind", default="rademacher", choices=["rademacher", "z4"])
     ap.add_argument("--lanes", type=int, default=0, help="override lanes per block row (tuning)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="0 disables the cpu_baseline leg")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="0 disables the cpu_baseline leg (--full only)")
     ap.add_argument("--temperature", type=float, default=0.5)
-    ap.add_argument("--user-calls", type=int, default=1, help="0 skips the wall times of free_energy / diagonalize / ldos through the Python API")
+    ap.add_argument("--user-calls", type=int, default=1,
+                    help="0 skips the wall times of free_energy / diagonalize / ldos through the Python API (--full only)")
     ap.add_argument("--model", default="swave", choices=["swave", "dwave", "potential", "texture", "ssd", "peierls", "landau"])
     ap.add_argument("--mode", default="vectors", choices=["vectors", "slab"],
                     help="vectors: H replicated, start vectors sharded (weak scaling, headline); "
@@ -391,6 +398,12 @@ def main():
     ap.add_argument("--allow-gloo", action="store_true",
                     help="if RCCL cannot be initialised, do the script's reductions on the host instead of failing "
                          "(rehearsal of the launch path only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline, the comparison passes (other "
+                         "matrices and kernels) and the wall times through the Python API")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed call, write what it returned to DIR/moments.npy and the free-energy estimate "
+                         "made from it to DIR/free_energy.npy (float64)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -435,7 +448,7 @@ def main():
     assert not system._devices, "the host assembly must not create a device mirror (CPU baseline forks workers next)"
 
     cpu_record = None
-    if args.cpu_seconds > 0 and args.gpus == 1 and rank == 0:
+    if args.full and args.cpu_seconds > 0 and args.gpus == 1 and rank == 0:
         cpu_record = cpu_baseline(system, scale, r_local, kind, args.cpu_seconds)  # before any GPU call
 
     backend.load()
@@ -566,24 +579,43 @@ def main():
         record["distinct_blocks_total"] = "> 256" if pf["dict_skipped"] == 1 else pf["dict_blocks"]
         return record
 
-    # Order: the comparison passes run first, the headline last.  The multi-step sweep kernels are
+    def settle(seconds):
+        """Keep the GPU busy with the headline call for `seconds` (the slowest rank decides, so every rank makes the
+        same number of calls and the collectives inside them pair up)."""
+        start = time.perf_counter()
+        while True:
+            run(63)
+            busy = time.perf_counter() - start
+            if comm is not None:
+                busy = float(comm.allreduce_max(np.array([busy]))[0])
+            if busy >= seconds:
+                return
+
+    # Order: the comparison passes (--full) run first, the headline last.  The multi-step sweep kernels are
     # sensitive to the shader clock, which takes ~50 ms of continuous load to settle after idle
     # (launch time 270 -> 247 us between an 8-step and a 512-step warm-up, DESIGN.md §8); the
-    # comparison passes are bandwidth-bound and lose 1-2 % in that phase.  The headline's own W
-    # warm-up steps still directly precede its K timed steps.
+    # comparison passes are bandwidth-bound and lose 1-2 % in that phase.  Without them, half a second
+    # of the headline call itself gives the clock the same load.  The headline's own W warm-up steps
+    # still directly precede its K timed steps.
     if args.warmup > 0:
         run(args.warmup)
     probe = solver.perf()  # which kernel family the default route takes on this matrix
-    position_pass = other_matrix("potential", VEC_RADEMACHER) if world == 1 and args.model == "swave" else None
-    texture_pass = other_matrix("texture", VEC_Z4) if world == 1 and args.model == "swave" else None
-    ssd_pass = other_matrix("ssd", VEC_RADEMACHER) if world == 1 and args.model == "swave" else None
-    landau_pass = other_matrix("landau", VEC_Z4) if world == 1 and args.model == "swave" else None
-    complex_one_step = (alternative({"BODGE_AMD_SWEEP": "0", "BODGE_AMD_DICT": "0", "BODGE_AMD_REAL": "0"})
-                        if probe["real_arithmetic"] else None)
-    complex_sweep = alternative({"BODGE_AMD_REAL": "0"}) if probe["real_arithmetic"] and probe["steps_per_launch"] >= 2 else None
-    streamed_one_step = alternative({"BODGE_AMD_SWEEP": "0", "BODGE_AMD_DICT": "0"}) if probe["dict_blocks"] else None
-    one_step_pass = alternative({"BODGE_AMD_SWEEP": "0"}) if probe["steps_per_launch"] >= 2 or probe["rolling"] else None
-    two_step_pass = alternative({"BODGE_AMD_SWEEP_STEPS": "2"}) if probe["steps_per_launch"] == 3 else None
+    position_pass = texture_pass = ssd_pass = landau_pass = None
+    complex_one_step = complex_sweep = streamed_one_step = one_step_pass = two_step_pass = None
+    if args.full:
+        if world == 1 and args.model == "swave":
+            position_pass = other_matrix("potential", VEC_RADEMACHER)
+            texture_pass = other_matrix("texture", VEC_Z4)
+            ssd_pass = other_matrix("ssd", VEC_RADEMACHER)
+            landau_pass = other_matrix("landau", VEC_Z4)
+        complex_one_step = (alternative({"BODGE_AMD_SWEEP": "0", "BODGE_AMD_DICT": "0", "BODGE_AMD_REAL": "0"})
+                            if probe["real_arithmetic"] else None)
+        complex_sweep = alternative({"BODGE_AMD_REAL": "0"}) if probe["real_arithmetic"] and probe["steps_per_launch"] >= 2 else None
+        streamed_one_step = alternative({"BODGE_AMD_SWEEP": "0", "BODGE_AMD_DICT": "0"}) if probe["dict_blocks"] else None
+        one_step_pass = alternative({"BODGE_AMD_SWEEP": "0"}) if probe["steps_per_launch"] >= 2 or probe["rolling"] else None
+        two_step_pass = alternative({"BODGE_AMD_SWEEP_STEPS": "2"}) if probe["steps_per_launch"] == 3 else None
+    else:
+        settle(0.5)
     if args.warmup > 0:
         run(args.warmup)
     mu, elapsed, perf = timed(args.steps)
@@ -593,9 +625,17 @@ def main():
             store.finish()
         return
 
+    free_energy = chebyshev.free_energy_series(mu / total_vectors, scale, args.temperature)
+    if args.dump_outputs:
+        # what the timed call returned (the moment vector, summed over vectors and ranks) and the estimate made from it
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "moments.npy"), np.asarray(mu, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "free_energy.npy"), np.array([free_energy], dtype=np.float64))
+
     # The calls a user of the reference makes, through the Python API, timed as wall time after the headline (never
     # `value`; N = 1 only): BASELINE's metric ends "free_energy wall-time" (VERDICT r3 item 4).
-    user_calls = user_facing_wall_times(system, shape) if world == 1 and args.model == "swave" and args.user_calls else None
+    user_calls = (user_facing_wall_times(system, shape)
+                  if args.full and world == 1 and args.model == "swave" and args.user_calls else None)
 
     value = total_vectors * args.steps / elapsed
     launch_ms = perf["kernel_ms"] / max(1, perf["launches"])
@@ -607,7 +647,6 @@ def main():
     # either stream, `launch_ms` the duration of one launch on its own stream (kernel_ms / launches - what rocprofv3
     # reports per kernel; two are in flight at a time, so launches x launch_ms = streams x window_ms).
     achieved = perf["bytes_moved"] / (perf["window_ms"] * 1e-3) / 1e9
-    free_energy = chebyshev.free_energy_series(mu / total_vectors, scale, args.temperature)
     kernel_name = kernel_label(perf)
     model_label = {"swave": "s-wave+Zeeman", "dwave": "d-wave"}[args.model]
     record = {
@@ -671,8 +710,10 @@ def main():
             "strip_rows": perf["strip_rows"],
             "distinct_blocks": perf["dict_blocks"],
         },
-        "pass_order": "comparison passes (other matrices, complex128, streamed, one-step, two-step) first, then W warm-up "
-                      "steps and the K timed steps of the headline kernel",
+        "pass_order": ("comparison passes (other matrices, complex128, streamed, one-step, two-step) first, then W warm-up "
+                       "steps and the K timed steps of the headline kernel" if args.full else
+                       "0.5 s of the headline call (clock settle), then W warm-up steps and the K timed steps of the "
+                       "headline kernel; no comparison passes (--full)"),
         "free_energy_wall_s": elapsed,
         "free_energy_estimate": free_energy,
         "user_facing_calls": user_calls,

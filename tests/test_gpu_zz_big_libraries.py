@@ -109,7 +109,7 @@ def test_rccl_single_rank_communicator(hip_library, rccl_library):
 
 @pytest.mark.timeout(600)
 def test_bench_launch_path_with_two_ranks_on_one_gpu(rccl_library):
-    """`bench.py --gpus 2` with the environment a `torch.distributed.run` launch gives its ranks (RANK, LOCAL_RANK,
+    """`bench.py --gpus 2 --full` with the environment a `torch.distributed.run` launch gives its ranks (RANK, LOCAL_RANK,
     WORLD_SIZE, MASTER_ADDR, MASTER_PORT - all the script reads; the launcher itself is exercised by the CPU test
     test_rccl_rendezvous_under_torchrun, and importing torch on a cold box costs minutes this suite does not have),
     rehearsed on this one-GPU box with --allow-gloo: both ranks map to GPU 0, RCCL refuses the duplicate device,
@@ -126,7 +126,7 @@ def test_bench_launch_path_with_two_ranks_on_one_gpu(rccl_library):
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--allow-gloo", "--lattice", "64,64,1",
-           "--steps", "12", "--warmup", "3", "--cpu-seconds", "0"]
+           "--steps", "12", "--warmup", "3", "--cpu-seconds", "0", "--full"]
     ranks = []
     for rank in range(2):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", LOCAL_WORLD_SIZE="2",

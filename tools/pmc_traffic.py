@@ -2,8 +2,8 @@
 """Turn rocprofv3 PMC passes into per-launch HBM traffic of the recurrence kernel.
 
     # on the GPU box, one pass per counter (FETCH_SIZE and WRITE_SIZE do not fit one pass):
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_FETCH_SIZE -- python3 bench.py --steps 8 --warmup 2 --cpu-seconds 0
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_WRITE_SIZE -- python3 bench.py --steps 8 --warmup 2 --cpu-seconds 0
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_FETCH_SIZE -- python3 bench.py --full --steps 8 --warmup 2 --cpu-seconds 0
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_WRITE_SIZE -- python3 bench.py --full --steps 8 --warmup 2 --cpu-seconds 0
     # then, anywhere:
     python3 tools/pmc_traffic.py OUT/pmc_FETCH_SIZE OUT/pmc_WRITE_SIZE --workload "1000x1000x1 R=8" --out profiles/traffic.json
 
