@@ -52,6 +52,7 @@ class Perf(C.Structure):
         ("sweeps", C.c_int64),
         ("persistent", C.c_int32),
         ("groups_per_launch", C.c_int32),
+        ("clenshaw", C.c_int32),
     ]
 
 
@@ -83,6 +84,10 @@ SIGNATURES = {
     "bdg_cheb_moments": (
         C.c_int,
         [_handle, _handle, C.c_double, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, _f64p],
+    ),
+    "bdg_fermi_blocks": (
+        C.c_int,
+        [_handle, C.c_double, C.c_int32, _f64p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _f64p],
     ),
     "bdg_cheb_diag_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p]),
     "bdg_lanczos_begin": (C.c_int, [_handle, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),

@@ -9,7 +9,8 @@ the bookkeeping around them:
                         ±-symmetric spectrum is the reference's
                         -½Σ_{ε>0}ε - TΣ_{ε>0}log(1+e^{-ε/T})  (ref hamiltonian.py:305-321)
 * `resolvent_series`    <e|(z-H)^{-1}|e> from per-vector moments (LDOS, ref :367-382)
-* `moments_for_*`       how many moments a requested accuracy needs
+* `moments_for_*`       how many moments a requested accuracy needs (`moments_for_fermi`: the
+                        coefficients of the Fermi function behind `fermi.fermi_matrix`)
 """
 
 from __future__ import annotations
@@ -159,6 +160,30 @@ def moments_for_free_energy(scale: float, temperature: float, digits: float = 11
             "(pass moments=... to override)", RuntimeWarning, stacklevel=3)
     m = int(np.clip(m, 32, MAX_MOMENTS))
     return m + (m & 1)
+
+
+def fermi_function(eps, temperature: float):
+    """f(ε) = 1 / (1 + exp(ε/T)) for T > 0, as ½(1 - tanh(ε/2T)) (no overflow at |ε| >> T)."""
+    return 0.5 * (1.0 - np.tanh(np.asarray(eps, dtype=float) / (2.0 * temperature)))
+
+
+def moments_for_fermi(scale: float, temperature: float, digits: float = 12.0) -> int:
+    """Number M of Chebyshev coefficients of the Fermi function f on [-a, a] for ~10^-digits truncation error.
+
+    f has its poles nearest to the real axis at ε = ±iπT, i.e. at x = ±iπT/a on [-1, 1]; the Bernstein
+    ellipse through them has ln ρ = asinh(πT/a), and the coefficients decay like ρ^-m (with a prefactor
+    below 2).  M = 1.02·(digits·ln 10 + ln 2) / ln ρ + 16 ≈ digits·ln10·a/(πT): the 2 % and the 16 cover
+    what the estimate drops (digits = 12 reaches 1e-11 on dense f(H), tests/test_fermi_host.py)."""
+    if temperature <= 0:
+        raise ValueError("The Chebyshev expansion of the Fermi function needs T > 0")
+    rate = np.arcsinh(np.pi * temperature / scale)
+    m = int(np.ceil(1.02 * (digits * np.log(10.0) + np.log(2.0)) / rate)) + 16
+    if m > MAX_MOMENTS:
+        import warnings
+
+        warnings.warn(f"T/scale = {temperature / scale:.1e} asks for {m} Chebyshev coefficients; capped at {MAX_MOMENTS} "
+                      "(pass moments=... to override, or method='dense')", RuntimeWarning, stacklevel=3)
+    return int(np.clip(m, 32, MAX_MOMENTS))
 
 
 def moments_for_resolvent(scale: float, gamma: float, digits: float = 12.0) -> int:

@@ -58,6 +58,7 @@
 #include "plans.hpp"
 #include "libraries.hpp"
 #include "recurrence.hpp"
+#include "fermi.hpp"
 #include "lanczos.hpp"
 #include "dense.hpp"
 #include "tridiag.hpp"
@@ -652,6 +653,13 @@ int bdg_cheb_dots_unit(bdg_system* sys, double scale, int32_t n_steps, int32_t n
     StartSpec start{StartKind::Unit};
     start.rows = rows;
     return run_recurrence(sys, scale, n_steps, n_vectors, start, d_out, e_out);
+}
+
+int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const double* coef, int32_t n_colours,
+                     const int32_t* site_colour, int32_t n_components, const int32_t* pat_indptr,
+                     const int32_t* pat_indices, double* blocks_out) {
+    return run_fermi_blocks(sys, scale, n_moments, coef, n_colours, site_colour, n_components, pat_indptr, pat_indices,
+                            blocks_out);
 }
 
 int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_moments,

@@ -1,0 +1,650 @@
+// fermi.hpp - the local one-body density matrix f(H) on the Hamiltonian's block pattern (bdg_fermi_blocks)
+// Part of the single translation unit bodge_hip.hip (included after recurrence.hpp): the kernels live in
+// namespace bdg beside the recurrence kernels, the driver in the unnamed namespace beside run_recurrence.
+//
+// Probing + Clenshaw.  The sites are coloured so that two sites of one colour are far apart
+// in the graph of H; for colour c and Nambu component β the probe vector is r = Σ_{i ∈ c} e_{4i+β}, and
+//     b_{M} = b_{M+1} = 0,   b_k = 2 H~ b_{k+1} - b_{k+2} + c_k r   (k = M-1 .. 1),   y = H~ b_1 - b_2 + c_0 r
+// (H~ = H / scale) gives y = Σ_k c_k T_k(H~) r = f(H) r, whose rows 4j..4j+3 are column β of the block
+// F_ji for every pattern block (j, i) with i of colour c.  A Clenshaw step moves what a recurrence step moves
+// (read b_{k+1} around the row, read b_{k+2}, write b_k in place of it) plus one int32 colour per block row;
+// the source term c_k r is made in registers from that colour, and no dot product is formed.
+#pragma once
+
+namespace bdg {
+
+// What a Clenshaw launch reads besides a recurrence step's arguments.  Vector v of a batch is probe
+// (colour colour_base + (v >> comp_shift), Nambu component v & ((1 << comp_shift) - 1)); vectors from
+// n_active on are padding and stay zero.
+struct ClenshawArgs {
+    StepArgs s;               // matrix, vector buffers, tiles; partial / discard / col_* are not read
+    const int* site_colour;   // [nb] colour of every block row
+    double source;            // c_k: the coefficient this launch adds on the probe entries
+    int colour_base;
+    int comp_shift;           // 1: components 0, 1 (electron columns), 2: all four
+    int n_active;
+};
+
+// nx[al] += c_k on the entries where the probe vectors of lane payload r are 1: row `colour` matches the
+// vector's colour and al its component.  PER_LANE = 1: .x is the real part of vector r; 2: .x / .y are
+// vectors 2r, 2r+1.  Compares instead of indexing keep nx in registers.
+template <int PER_LANE>
+__device__ inline void add_source(double2 nx[4], const ClenshawArgs& a, int colour, int r) {
+    const int mask = (1 << a.comp_shift) - 1;
+#pragma unroll
+    for (int q = 0; q < PER_LANE; ++q) {
+        const int v = PER_LANE * r + q;
+        const bool hit = v < a.n_active && colour == a.colour_base + (v >> a.comp_shift);
+        const int comp = v & mask;
+#pragma unroll
+        for (int al = 0; al < 4; ++al) {
+            const double add = hit && comp == al ? a.source : 0.0;
+            if (q == 0) nx[al].x += add;
+            else nx[al].y += add;
+        }
+    }
+}
+
+// Generic form: cheb_step's tile loop (LDS staging of the streamed blocks, gathers of b_{k+1}) with the
+// Clenshaw epilogue b_k = coef * (H b_{k+1}) - b_{k+2} + c_k r.
+template <typename Mode, int RL>
+__global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw(ClenshawArgs ca) {
+    extern __shared__ double2 lds[];
+    const StepArgs& a = ca.s;
+    constexpr int RW = kWave / RL;
+    constexpr int SPB = Mode::kSlotsPerBlock;
+    constexpr int STRIDE = Mode::kBlockStride;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const int s = lane / RL;
+    const int r = lane % RL;
+    const int region = a.stage_blocks * STRIDE;
+    double2* stage = lds + wave * region;
+    const double2* all_blocks = static_cast<const double2*>(a.blocks);
+
+    const int xcd = blockIdx.x & 7;
+    const int slot = blockIdx.x >> 3;
+    const int slots = gridDim.x >> 3;
+    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
+    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
+
+    for (int t = t_lo + slot; t < t_hi; t += slots) {
+        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
+        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
+        const int row0 = (tile * kWavesPerBlock + wave) * RW;
+        if (row0 >= a.nb) continue;
+        const int row_end = min(row0 + RW, a.nb);
+        const int kb0 = a.indptr[row0];
+        const int kb1 = a.indptr[row_end];
+
+        const int i = row0 + s;
+        const bool valid = i < a.nb;
+        int kbeg = 0, kend = 0, colour = -1;
+        if (valid) {
+            kbeg = a.indptr[i];
+            kend = a.indptr[i + 1];
+            colour = ca.site_colour[i];
+        }
+        double2 acc[4];
+#pragma unroll
+        for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
+
+        for (int c0 = kb0; c0 < kb1; c0 += a.stage_blocks) {
+            const int c1 = min(c0 + a.stage_blocks, kb1);
+            const int n_el = (c1 - c0) * SPB;
+            const double2* src = all_blocks + (size_t)c0 * SPB;
+            for (int e0 = 0; e0 < n_el; e0 += 4 * kWave) {
+                double2 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int e = e0 + u * kWave + lane;
+                    if (e < n_el) v[u] = load_stream(src + e);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int e = e0 + u * kWave + lane;
+                    if (e < n_el) stage[(e / SPB) * STRIDE + (e % SPB)] = v[u];
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+            const int k0 = max(kbeg, c0), k1 = min(kend, c1);
+            double2 x[4], xn[4];
+            if (k0 < k1) {
+                const size_t j = (size_t)a.indices[k0];
+#pragma unroll
+                for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
+            }
+            for (int k = k0; k < k1; ++k) {
+#pragma unroll
+                for (int be = 0; be < 4; ++be) x[be] = xn[be];
+                if (k + 1 < k1) {
+                    const size_t j = (size_t)a.indices[k + 1];
+#pragma unroll
+                    for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
+                }
+                Mode::mac_row(acc, stage + (k - c0) * STRIDE, x);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+        }
+
+        if (valid) {
+            double2 nx[4];
+#pragma unroll
+            for (int al = 0; al < 4; ++al) {
+                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
+                const double2 p = (a.stream_vectors & 1) ? load_stream(a.prev + own) : a.prev[own];
+                nx[al].x = fma(a.coef, acc[al].x, -p.x);
+                nx[al].y = fma(a.coef, acc[al].y, -p.y);
+            }
+            add_source<Mode::kVec>(nx, ca, colour, r);
+#pragma unroll
+            for (int al = 0; al < 4; ++al) {
+                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
+                if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
+                else a.prev[own] = nx[al];
+            }
+        }
+    }
+}
+
+// Dictionary form: cheb_step_dict's tile loop (block table in LDS, fixed-width row words, own and
+// neighbouring rows of b_{k+1} shared through LDS) with the Clenshaw epilogue.
+template <typename Mode, int RL, int MAXB>
+__global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw_dict(ClenshawArgs ca) {
+    extern __shared__ double2 lds[];
+    const StepArgs& a = ca.s;
+    constexpr int RW = kWave / RL;
+    constexpr int SPB = Mode::kSlotsPerBlock;
+    constexpr int STRIDE = Mode::kBlockStride;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    const int s = lane / RL;
+    const int r = lane % RL;
+
+    const double2* table = static_cast<const double2*>(a.dict_table);
+    for (int e = threadIdx.x; e < a.n_unique * SPB; e += kBlockThreads)
+        lds[(e / SPB) * STRIDE + (e % SPB)] = table[e];
+    double2* share = lds + a.n_unique * STRIDE + wave * (kWave * 4);
+    __syncthreads();
+
+    const int xcd = blockIdx.x & 7;
+    const int slot = blockIdx.x >> 3;
+    const int slots = gridDim.x >> 3;
+    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
+    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
+    auto first_row = [&](int t) {
+        if (t >= t_hi) return a.nb;
+        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
+        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
+        return (tile * kWavesPerBlock + wave) * RW;
+    };
+    struct RowMeta {
+        int len;
+        unsigned word[MAXB];
+    };
+    auto col_of = [](unsigned w) { return (size_t)(w & 0xFFFFFFu); };
+    auto id_of = [](unsigned w) { return (int)(w >> 24); };
+    constexpr int ELLW = MAXB <= 3 ? 4 : 8;
+    auto load_meta = [&](int row0, RowMeta& m) {
+        const int i = row0 + s;
+        const uint4* src = reinterpret_cast<const uint4*>(a.dict_ell) + (size_t)min(i, a.nb - 1) * (ELLW / 4);
+        unsigned words[8];
+        const uint4 lo = src[0];
+        words[0] = lo.x, words[1] = lo.y, words[2] = lo.z, words[3] = lo.w;
+        if constexpr (ELLW == 8) {
+            const uint4 hi = src[1];
+            words[4] = hi.x, words[5] = hi.y, words[6] = hi.z, words[7] = hi.w;
+        } else {
+            words[4] = words[5] = words[6] = words[7] = 0xFFFFFFFFu;
+        }
+        m.len = 0;
+#pragma unroll
+        for (int q = 0; q < MAXB; ++q) {
+            const bool there = i < a.nb && words[q] != 0xFFFFFFFFu;
+            m.len += there ? 1 : 0;
+            m.word[q] = there ? words[q] : 0u;
+        }
+    };
+
+    int pos = t_lo + slot;
+    int row0 = first_row(pos);
+    RowMeta meta;
+    load_meta(row0, meta);
+    for (; pos < t_hi; pos += slots) {
+        const int row0_n = first_row(pos + slots);
+        RowMeta meta_n;
+        load_meta(row0_n, meta_n);
+
+        const int i = row0 + s;
+        const bool valid = i < a.nb;
+        {
+            double2 own[4];
+#pragma unroll
+            for (int be = 0; be < 4; ++be)
+                own[be] = valid ? a.cur[vslot(be, (size_t)i, r, a.ncols, RL)] : make_double2(0.0, 0.0);
+#pragma unroll
+            for (int be = 0; be < 4; ++be) share[SHARE_SLOT(lane, be)] = own[be];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+        if (valid) {
+            auto source = [&](unsigned w) {
+                const long d = (long)col_of(w) - (long)i;
+                const long ss = (long)s + d;
+                return (ss >= 0 && ss < RW && (long)i + d < a.nb) ? (int)d : (int)kWave;
+            };
+            const int colour = ca.site_colour[i];
+            double2 acc[4], x[4], xn[4];
+#pragma unroll
+            for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
+            if (meta.len > 0 && source(meta.word[0]) == kWave) {
+#pragma unroll
+                for (int be = 0; be < 4; ++be)
+                    xn[be] = a.cur[vslot(be, col_of(meta.word[0]), r, a.ncols, RL)];
+            }
+#pragma unroll
+            for (int q = 0; q < MAXB; ++q) {
+                if (q < meta.len) {
+                    const int src = source(meta.word[q]);
+                    if (src == kWave) {
+#pragma unroll
+                        for (int be = 0; be < 4; ++be) x[be] = xn[be];
+                    } else {
+#pragma unroll
+                        for (int be = 0; be < 4; ++be) x[be] = share[SHARE_SLOT(lane + src * RL, be)];
+                    }
+                    if (q + 1 < MAXB && q + 1 < meta.len && source(meta.word[q + 1 < MAXB ? q + 1 : 0]) == kWave) {
+#pragma unroll
+                        for (int be = 0; be < 4; ++be)
+                            xn[be] = a.cur[vslot(be, col_of(meta.word[q + 1 < MAXB ? q + 1 : 0]), r, a.ncols, RL)];
+                    }
+                    Mode::mac_row(acc, lds + id_of(meta.word[q]) * STRIDE, x);
+                }
+            }
+            double2 p[4];
+            if (a.stream_vectors & 1) {
+#pragma unroll
+                for (int al = 0; al < 4; ++al) p[al] = load_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL));
+            } else {
+#pragma unroll
+                for (int al = 0; al < 4; ++al) p[al] = a.prev[vslot(al, (size_t)i, r, a.ncols, RL)];
+            }
+#pragma unroll
+            for (int al = 0; al < 4; ++al) {
+                p[al].x = fma(a.coef, acc[al].x, -p[al].x);
+                p[al].y = fma(a.coef, acc[al].y, -p[al].y);
+            }
+            add_source<Mode::kVec>(p, ca, colour, r);
+            if (a.stream_vectors & 2) {
+#pragma unroll
+                for (int al = 0; al < 4; ++al) store_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL), p[al]);
+            } else {
+#pragma unroll
+                for (int al = 0; al < 4; ++al) a.prev[vslot(al, (size_t)i, r, a.ncols, RL)] = p[al];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        row0 = row0_n;
+        meta = meta_n;
+    }
+}
+
+// Columns of the pattern blocks whose column site has a colour of the batch, from the batch's final y:
+//   out[k][al][b] = y[al][j][v],   v = (colour - colour_base) << comp_shift | b
+// for entry e = (block k, block row j, colour) of the per-colour list and b < 1 << comp_shift.  One thread
+// per (entry, al, b); the entries of one batch are a contiguous range of the list.  PER_LANE = 2: real
+// payloads, vector v in component v & 1 of payload v >> 1.
+template <int PER_LANE>
+__global__ void fermi_extract(const double2* __restrict__ y, int64_t nb, int rl, const int* __restrict__ ent_block,
+                              const int* __restrict__ ent_row, const int* __restrict__ ent_colour, int64_t n_ent,
+                              int colour_base, int comp_shift, double2* __restrict__ out) {
+    const int64_t per_entry = (int64_t)4 << comp_shift;
+    const int64_t total = n_ent * per_entry;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = idx / per_entry;
+        const int rest = (int)(idx - e * per_entry);
+        const int al = rest >> comp_shift;
+        const int b = rest & ((1 << comp_shift) - 1);
+        const int v = ((ent_colour[e] - colour_base) << comp_shift) | b;
+        const size_t at = vslot(al, (size_t)ent_row[e], v / PER_LANE, (size_t)nb, rl);
+        double2 value;
+        if (PER_LANE == 2) {
+            const double2 pair = y[at];
+            value = make_double2((v & 1) ? pair.y : pair.x, 0.0);
+        } else {
+            value = y[at];
+        }
+        out[(size_t)ent_block[e] * 16 + al * 4 + b] = value;
+    }
+}
+
+}  // namespace bdg
+
+namespace {
+
+using ClenshawKernel = void (*)(bdg::ClenshawArgs);
+
+template <typename Mode>
+ClenshawKernel clenshaw_generic_for(int rl) {
+    switch (rl) {
+        case 4: return bdg::cheb_clenshaw<Mode, 4>;
+        case 8: return bdg::cheb_clenshaw<Mode, 8>;
+        case 16: return bdg::cheb_clenshaw<Mode, 16>;
+        case 32: return bdg::cheb_clenshaw<Mode, 32>;
+        case 64: return bdg::cheb_clenshaw<Mode, 64>;
+    }
+    return nullptr;
+}
+
+template <typename Mode, int MAXB>
+ClenshawKernel clenshaw_dict_for(int rl) {
+    switch (rl) {
+        case 4: return bdg::cheb_clenshaw_dict<Mode, 4, MAXB>;
+        case 8: return bdg::cheb_clenshaw_dict<Mode, 8, MAXB>;
+        case 16: return bdg::cheb_clenshaw_dict<Mode, 16, MAXB>;
+        case 32: return bdg::cheb_clenshaw_dict<Mode, 32, MAXB>;
+    }
+    // (64 lanes: complex modes only, as for the one-step dictionary kernel)
+    if constexpr (Mode::kVec == 1)
+        if (rl == 64) return bdg::cheb_clenshaw_dict<Mode, 64, MAXB>;
+    return nullptr;
+}
+
+template <typename Mode>
+ClenshawKernel clenshaw_kernel_for(bool dictionary, int max_row_blocks, int rl) {
+    if (!dictionary) return clenshaw_generic_for<Mode>(rl);
+    if (max_row_blocks <= 3) return clenshaw_dict_for<Mode, 3>(rl);
+    if (max_row_blocks <= 5) return clenshaw_dict_for<Mode, 5>(rl);
+    return clenshaw_dict_for<Mode, 7>(rl);
+}
+
+ClenshawKernel clenshaw_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
+    switch (mode.id) {
+        case 1: return clenshaw_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
+        case 2: return clenshaw_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
+        case 3: return clenshaw_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
+    }
+    return clenshaw_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
+}
+
+// Launch plan of the Clenshaw kernels: the one-step recurrence's choice between the dictionary and the
+// streamed-block form (dict_kernel decides, as in make_plan), its tiles and its LDS, without the space of the
+// dot reduction.  The pipelined one-step form has no Clenshaw twin: a matrix that would take it runs the
+// generic form.
+struct ClenshawPlan {
+    StepPlan step;  // tiles, grid, LDS, mode, dictionary flag (step.kernel unused)
+    ClenshawKernel kernel = nullptr;
+};
+
+int make_clenshaw_plan(bdg_system* sys, int rl, const ModeInfo& mode, ClenshawPlan* out) {
+    StepPlan& plan = out->step;
+    plan = StepPlan{};
+    plan.rl = rl;
+    plan.mode = mode;
+    const int rows_per_wave = bdg::kWave / rl;
+    plan.rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
+    plan.n_tiles = (int)((sys->nb + plan.rows_per_tile - 1) / plan.rows_per_tile);
+    plan.dictionary = dict_kernel(sys, mode, rl) != nullptr;
+    out->kernel = clenshaw_kernel(mode, plan.dictionary, sys->max_row_blocks, rl);
+    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the Clenshaw kernels", rl);
+    if (plan.dictionary) {
+        plan.lds_bytes = plan.lds_footprint = (size_t)sys->n_unique * mode.stride * sizeof(double2) +
+                                              (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
+    } else {
+        const int tile_blocks = rows_per_wave * std::max(1, sys->max_row_blocks);
+        const int cap = (int)((160 * 1024 / bdg::kWavesPerBlock) / (mode.stride * sizeof(double2)));
+        plan.stage_blocks = std::max(1, std::min(tile_blocks, cap));
+        plan.lds_bytes = plan.lds_footprint =
+            (size_t)bdg::kWavesPerBlock * plan.stage_blocks * mode.stride * sizeof(double2);
+        if (plan.lds_bytes > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(out->kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    }
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(out->kernel),
+                                                         bdg::kBlockThreads, plan.lds_bytes));
+    per_cu = std::max(1, std::min(per_cu, 8));
+    if (const char* cap = knob::raw("BODGE_AMD_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(cap));
+    const int grid = std::min(plan.n_tiles, per_cu * sys->num_cus);
+    plan.grid = std::max(8, (grid + 7) / 8 * 8);
+    return BDG_OK;
+}
+
+// HBM bytes of one Clenshaw launch: a recurrence launch's (same matrix stream, same three vector passes)
+// plus the int32 colour of every block row.
+double clenshaw_bytes(const bdg_system* sys, int vectors, const ModeInfo& mode, bool dictionary) {
+    return algorithmic_bytes(sys, vectors, mode, dictionary) + 4.0 * (double)sys->nb;
+}
+
+int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double* coef, int n_colours,
+                     const int32_t* site_colour, int n_components, const int32_t* pat_indptr,
+                     const int32_t* pat_indices, double* blocks_out) {
+    if (!sys) return fail(BDG_EINVAL, "null system handle");
+    if (!coef || !site_colour || !pat_indptr || !pat_indices || !blocks_out) return fail(BDG_EINVAL, "null argument");
+    if (sys->ncols != sys->nb || sys->row_offset != 0)
+        return fail(BDG_EINVAL, "bdg_fermi_blocks needs a whole (square) matrix: slabs are not supported");
+    if (!(scale > 0.0)) return fail(BDG_EINVAL, "scale must be positive");
+    if (n_moments < 1) return fail(BDG_EINVAL, "n_moments must be >= 1");
+    if (n_colours < 1) return fail(BDG_EINVAL, "n_colours must be >= 1");
+    if (n_components != 2 && n_components != 4) return fail(BDG_EINVAL, "n_components must be 2 or 4");
+    const int64_t nb = sys->nb;
+    if (pat_indptr[0] != 0) return fail(BDG_EINVAL, "pattern indptr must start at 0");
+    for (int64_t i = 0; i < nb; ++i)
+        if (pat_indptr[i + 1] < pat_indptr[i]) return fail(BDG_EINVAL, "pattern indptr is not monotone");
+    const int64_t n_pat = pat_indptr[nb];
+    for (int64_t k = 0; k < n_pat; ++k)
+        if (pat_indices[k] < 0 || pat_indices[k] >= nb) return fail(BDG_EINVAL, "pattern column %d out of range", pat_indices[k]);
+    for (int64_t i = 0; i < nb; ++i)
+        if (site_colour[i] >= n_colours) return fail(BDG_EINVAL, "site colour %d out of range", site_colour[i]);
+    lanczos_free(sys);
+    HIP_TRY(hipSetDevice(sys->device));
+
+    // Per-colour list of the pattern blocks (k, row j) whose column site i has that colour (counting sort);
+    // a site with a negative colour is not probed by this call (the caller shares the colours out).
+    std::vector<int64_t> colour_ptr((size_t)n_colours + 1, 0);
+    for (int64_t k = 0; k < n_pat; ++k)
+        if (site_colour[pat_indices[k]] >= 0) ++colour_ptr[(size_t)site_colour[pat_indices[k]] + 1];
+    for (int c = 0; c < n_colours; ++c) colour_ptr[(size_t)c + 1] += colour_ptr[(size_t)c];
+    const int64_t n_ent = colour_ptr[(size_t)n_colours];
+    std::vector<int32_t> ent_block((size_t)std::max<int64_t>(1, n_ent)), ent_row(ent_block.size()), ent_colour(ent_block.size());
+    {
+        std::vector<int64_t> fill(colour_ptr.begin(), colour_ptr.end() - 1);
+        for (int64_t j = 0; j < nb; ++j)
+            for (int64_t k = pat_indptr[j]; k < pat_indptr[j + 1]; ++k) {
+                const int c = site_colour[pat_indices[k]];
+                if (c < 0) continue;
+                const int64_t at = fill[(size_t)c]++;
+                ent_block[(size_t)at] = (int32_t)k;
+                ent_row[(size_t)at] = (int32_t)j;
+                ent_colour[(size_t)at] = c;
+            }
+    }
+
+    // Arithmetic and storage mode as for a recurrence with real start vectors (the probes are 0 / 1).
+    const char* real_env = knob::raw("BODGE_AMD_REAL");
+    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
+    const char* ph_env = knob::raw("BODGE_AMD_PH");
+    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const int per_lane = mode.per_lane;
+    // Vectors per batch: whole colours, the widest power of two up to 64 whose vector buffer stays within
+    // 96 MB (batch_width's rule); set_lanes_per_row fixes the lanes instead.
+    const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
+    int width = 64;
+    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
+    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
+    if (real && width > 64) width = 64;
+    const int colours_per_batch = std::max(1, std::min(n_colours, width / n_components));
+    const int n_active_max = colours_per_batch * n_components;
+    int rl = std::max(4, next_pow2((n_active_max + per_lane - 1) / per_lane));
+    if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= n_active_max) rl = sys->lanes_override;
+    const int rv = rl * per_lane;
+    ClenshawPlan cplan;
+    if (int rc = make_clenshaw_plan(sys, rl, mode, &cplan)) return rc;
+    const StepPlan& plan = cplan.step;
+    bdg::StepArgs base{};
+    if (int rc = matrix_args(sys, plan, &base)) return rc;
+    int strip_rows = 0;
+    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, (real ? 32.0 : 64.0) * rv, &base.tile_order,
+                                    &strip_rows))
+        return rc;
+    const size_t vec_count = (size_t)4 * nb * rl;
+    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
+    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
+    bool alternate = true;
+    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const int n_batches = (n_colours + colours_per_batch - 1) / colours_per_batch;
+
+    // Side by side on two of the handle's stream sets while one launch leaves the GPU part empty (the rule of
+    // run_recurrence for the one-step kernels); BODGE_AMD_STREAMS overrides.
+    int n_streams = (double)nb * rv <= kSideBySideOneStepLimit ? 2 : 1;
+    if (const char* env = knob::raw("BODGE_AMD_STREAMS")) n_streams = std::clamp(atoi(env), 1, 4);
+    n_streams = std::max(1, std::min(n_streams, n_batches));
+    while ((int)sys->side_sets.size() < n_streams - 1) {
+        auto side = std::make_unique<StreamSet>();
+        if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
+        sys->side_sets.push_back(std::move(side));
+    }
+    std::vector<StreamSet*> sets{sys};
+    for (int s = 1; s < n_streams; ++s) sets.push_back(sys->side_sets[(size_t)s - 1].get());
+    for (StreamSet* set : sets) {
+        if (int rc = set->vec_a.reserve(vec_count)) return rc;
+        if (int rc = set->vec_b.reserve(vec_count)) return rc;
+    }
+
+    DeviceBuffer<int> d_colour, d_block, d_row, d_ent_colour;
+    DeviceBuffer<double2> d_out;
+    std::vector<hipEvent_t> events;
+    auto body = [&]() -> int {
+        if (int rc = d_colour.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
+        if (int rc = d_block.reserve(ent_block.size())) return rc;
+        if (int rc = d_row.reserve(ent_block.size())) return rc;
+        if (int rc = d_ent_colour.reserve(ent_block.size())) return rc;
+        if (int rc = d_out.reserve((size_t)std::max<int64_t>(1, n_pat) * 16)) return rc;
+        hipStream_t st = sys->stream;
+        HIP_TRY(hipMemcpyAsync(d_colour.ptr, site_colour, sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_block.ptr, ent_block.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_row.ptr, ent_row.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_ent_colour.ptr, ent_colour.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_out.ptr, 0, sizeof(double2) * 16 * (size_t)n_pat, st));
+        // (tables, packed blocks and the uploads above are on the handle's stream: the side streams wait for them)
+        if (!sys->ev_side) HIP_TRY(hipEventCreateWithFlags(&sys->ev_side, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(sys->ev_side, st));
+        for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamWaitEvent(sets[(size_t)s]->stream, sys->ev_side, 0));
+        events.assign((size_t)2 * n_batches, nullptr);
+        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
+
+        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
+        bdg_perf perf{};
+        for (int first = 0; first < n_batches; first += n_streams) {
+            const int last = std::min(n_batches, first + n_streams);
+            std::vector<bdg::ClenshawArgs> args((size_t)(last - first));
+            std::vector<double2*> cur((size_t)(last - first)), prev((size_t)(last - first));
+            for (int b = first; b < last; ++b) {
+                StreamSet* set = sets[(size_t)(b - first)];
+                bdg::ClenshawArgs& ca = args[(size_t)(b - first)];
+                ca.s = base;
+                ca.site_colour = d_colour.ptr;
+                ca.colour_base = b * colours_per_batch;
+                ca.comp_shift = n_components == 4 ? 2 : 1;
+                ca.n_active = std::min(colours_per_batch, n_colours - ca.colour_base) * n_components;
+                cur[(size_t)(b - first)] = set->vec_a.ptr;
+                prev[(size_t)(b - first)] = set->vec_b.ptr;
+                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_a.ptr, (int64_t)vec_count);
+                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_b.ptr, (int64_t)vec_count);
+                HIP_TRY(hipEventRecord(events[(size_t)2 * b], set->stream));
+            }
+            // b_k for k = M-1 .. 1, then y: one launch per coefficient, the batches of the round in turn
+            for (int n = 0; n < n_moments; ++n) {
+                const int k = n_moments - 1 - n;
+                for (int b = first; b < last; ++b) {
+                    const size_t q = (size_t)(b - first);
+                    bdg::ClenshawArgs& ca = args[q];
+                    ca.s.cur = cur[q];
+                    ca.s.prev = prev[q];
+                    ca.s.coef = (k == 0 ? 1.0 : 2.0) / scale;
+                    ca.s.reverse = alternate ? (n & 1) : 0;
+                    ca.source = coef[k];
+                    cplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, sets[q]->stream>>>(ca);
+                    std::swap(cur[q], prev[q]);
+                }
+            }
+            for (int b = first; b < last; ++b) {
+                const size_t q = (size_t)(b - first);
+                HIP_TRY(hipEventRecord(events[(size_t)2 * b + 1], sets[q]->stream));
+                const int c0 = args[q].colour_base, c1 = c0 + args[q].n_active / n_components;
+                const int64_t e0 = colour_ptr[(size_t)c0], count = colour_ptr[(size_t)c1] - e0;
+                if (count > 0) {
+                    const int64_t total = count * 4 * n_components;
+                    const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
+                    if (real)
+                        bdg::fermi_extract<2><<<grid, 256, 0, sets[q]->stream>>>(
+                            cur[q], nb, rl, d_block.ptr + e0, d_row.ptr + e0, d_ent_colour.ptr + e0, count, c0,
+                            args[q].comp_shift, d_out.ptr);
+                    else
+                        bdg::fermi_extract<1><<<grid, 256, 0, sets[q]->stream>>>(
+                            cur[q], nb, rl, d_block.ptr + e0, d_row.ptr + e0, d_ent_colour.ptr + e0, count, c0,
+                            args[q].comp_shift, d_out.ptr);
+                }
+                perf.vector_steps += (int64_t)n_moments * args[q].n_active;
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        for (int s = 1; s < n_streams; ++s) {
+            HIP_TRY(hipEventRecord(sys->ev_side, sets[(size_t)s]->stream));
+            HIP_TRY(hipStreamWaitEvent(st, sys->ev_side, 0));
+        }
+        HIP_TRY(hipMemcpyAsync(blocks_out, d_out.ptr, sizeof(double2) * 16 * (size_t)n_pat, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        float window = 0.f;
+        for (int b = 0; b < n_batches; ++b) {
+            float t = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t, events[(size_t)2 * b], events[(size_t)2 * b + 1]));
+            perf.kernel_ms += t;
+            HIP_TRY(hipEventElapsedTime(&t, events[0], events[(size_t)2 * b + 1]));
+            window = std::max(window, t);
+        }
+        perf.window_ms = window;
+        perf.launches = (int64_t)n_batches * n_moments;
+        perf.bytes_per_launch = clenshaw_bytes(sys, rv, mode, plan.dictionary);
+        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
+        perf.lanes_per_row = rl;
+        perf.vectors_per_launch = rv;
+        perf.grid = plan.grid;
+        perf.lds_bytes = (int32_t)plan.lds_footprint;
+        perf.pipelined = 0;
+        perf.real_arithmetic = real ? 1 : 0;
+        perf.strip_rows = strip_rows;
+        perf.ph_packed = mode.ph ? 1 : 0;
+        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
+        perf.steps_per_launch = 1;
+        perf.dict_skipped = sys->dict_skipped;
+        perf.streams = n_streams;
+        perf.groups_per_launch = 1;
+        perf.clenshaw = plan.dictionary ? 2 : 1;
+        sys->perf = perf;
+        return BDG_OK;
+    };
+    const int rc = body();
+    if (rc) {
+        (void)hipStreamSynchronize(sys->stream);
+        for (auto& side : sys->side_sets) (void)hipStreamSynchronize(side->stream);
+    }
+    for (hipEvent_t ev : events)
+        if (ev) (void)hipEventDestroy(ev);
+    d_colour.release();
+    d_block.release();
+    d_row.release();
+    d_ent_colour.release();
+    d_out.release();
+    return rc;
+}
+
+}  // namespace

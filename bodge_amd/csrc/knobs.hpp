@@ -56,6 +56,9 @@
 //     BODGE_AMD_NO_PREFETCH                  no background read of the rocSOLVER / RCCL shared objects
 //     BODGE_AMD_TRACE                        timing lines on stderr
 //   (read by the Python side: BODGE_AMD_LIBRARY, BODGE_AMD_DEVICE, BODGE_AMD_HOST_NATIVE, BODGE_AMD_FORCE_COMM)
+//   bdg_fermi_blocks (fermi.hpp) has no switch of its own: it follows DICT, REAL, PH, STREAMS, STREAM_VECTORS, ALTERNATE,
+//   BLOCKS_PER_CU and L2_BUDGET as the one-step kernels do, and bdg_set_lanes_per_row fixes its batch width.  Its
+//   four-column form (no particle-hole halving, for tests) is the private keyword `_all_columns` of fermi_matrix.
 #pragma once
 
 #include <cstdlib>

@@ -491,6 +491,16 @@ class Hamiltonian:
 
         return lowest_eigenpairs(self, k, **options)
 
+    def fermi_matrix(self, temperature: float, **options):
+        """Local one-body density matrix: the blocks of f(H), f(ε) = 1/(1 + e^{ε/T}), on the block skeleton
+        of this Hamiltonian (every site and bond, zero blocks included), as a `FermiMatrix` with the
+        contractions density(), magnetization(), pair_amplitude(), pairing(i, j), expectation(dH).
+        Not part of the reference API; options (method, moments, digits, distance, devices) are those of
+        `bodge_amd.fermi.fermi_matrix`."""
+        from .fermi import fermi_matrix
+
+        return fermi_matrix(self, temperature, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

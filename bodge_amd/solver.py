@@ -208,6 +208,22 @@ class DeviceSolver:
         )
         return mu
 
+    def fermi_blocks(self, scale, coef, site_colour, n_colours, n_components, indptr, indices) -> np.ndarray:
+        """(nnzb, 4, 4) complex blocks of Σ_k coef[k] T_k(H/scale) on the pattern (indptr, indices) by probing with
+        the colouring `site_colour` (bdg_fermi_blocks); n_components = 2 fills the columns 0, 1 only."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        site_colour = np.ascontiguousarray(site_colour, dtype=np.int32)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        if site_colour.shape != (self.n_sites,) or indptr.shape != (self.n_sites + 1,) or indices.size != indptr[-1]:
+            raise ValueError("site colours and pattern must describe the handle's block rows")
+        out = np.empty((indices.size, 4, 4), dtype=np.complex128)
+        backend.check(self._lib.bdg_fermi_blocks(
+            self._handle, float(scale), coef.size, backend.as_f64p(coef), int(n_colours), backend.as_i32p(site_colour),
+            int(n_components), backend.as_i32p(indptr), backend.as_i32p(indices), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def lanczos_begin(self, n_vectors: int, seed: int = 0, first_id: int = 0, kind: int = VEC_RADEMACHER,
                       max_iter: int = 10000) -> None:
         """Start n_vectors independent Lanczos processes on H^2 (see `lanczos_advance`)."""

@@ -87,6 +87,8 @@ typedef struct bdg_perf {
                               steps) of `groups_per_launch` lane groups; its waves claim (sweep, group, unit) tasks and
                               start one as soon as the neighbouring units have published the sweep before */
     int32_t groups_per_launch; /* lane groups (batches of the call) advanced by one persistent launch, else 1 */
+    int32_t clenshaw;      /* bdg_fermi_blocks: 1 = its Clenshaw steps ran the streamed-block kernel (cheb_clenshaw),
+                              2 = the dictionary kernel (cheb_clenshaw_dict); 0 = the call was another one */
 } bdg_perf;
 
 const char* bdg_last_error(void);
@@ -165,6 +167,25 @@ int bdg_cheb_dots_unit(bdg_system* sys, double scale, int32_t n_steps, int32_t n
 int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_moments,
                      int32_t n_vectors, uint64_t seed, uint64_t first_vec_id, int32_t vec_kind,
                      double* mu_out);
+/*
+ * Blocks of the density matrix F = f(H) = sum_k coef[k] T_k(H/scale) on a block pattern, by probing
+ * (DESIGN.md §10).  site_colour[i] in [0, n_colours) colours the nb block rows (a negative colour leaves
+ * the site out of this call); the probe vector of colour c and Nambu component b is the sum of the unit
+ * vectors e_{4i+b} over the sites i of colour c, and f(H) applied to it (Clenshaw's recurrence, one launch
+ * per coefficient) gives column b of every pattern block whose column site has colour c:
+ *   blocks_out[((k*4 + a)*4 + b)*2 + {0, 1}] = (re, im) of [f(H) r_{c b}][4j + a]
+ * for block k = (block row j, column pat_indices[k]) of the pattern (pat_indptr[nb + 1], canonical order,
+ * any subset of block pairs).  Exact when two sites of one colour are farther apart in the graph of H
+ * than the expansion reaches; otherwise the blocks carry the contributions of the other sites of the
+ * colour.  n_components = 4 computes all columns, 2 the electron columns b = 0, 1 only (the caller
+ * derives the others from particle-hole symmetry; columns 2, 3 are then returned as 0).  Colours are
+ * batched (whole colours, up to 64 probe vectors per launch) on the handle's stream sets; bdg_perf_query
+ * reports the call (`clenshaw` says which kernel form ran).  Whole matrices only (not slabs).
+ */
+int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const double* coef, int32_t n_colours,
+                     const int32_t* site_colour, int32_t n_components, const int32_t* pat_indptr,
+                     const int32_t* pat_indices, double* blocks_out);
+
 /* Per-start-vector moments for unit vectors: mu_out[m*n_vectors + r]. */
 int bdg_cheb_diag_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_vectors,
                           const int64_t* rows, double* mu_out);
