@@ -59,6 +59,7 @@
 #include "libraries.hpp"
 #include "recurrence.hpp"
 #include "fermi.hpp"
+#include "green.hpp"
 #include "lanczos.hpp"
 #include "dense.hpp"
 #include "tridiag.hpp"
@@ -660,6 +661,11 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
                      const int32_t* pat_indices, double* blocks_out) {
     return run_fermi_blocks(sys, scale, n_moments, coef, n_colours, site_colour, n_components, pat_indptr, pat_indices,
                             blocks_out);
+}
+
+int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,
+                      int32_t n_targets, const int32_t* target_block_rows, double* out) {
+    return run_green_moments(sys, scale, n_moments, n_sources, source_rows, n_targets, target_block_rows, out);
 }
 
 int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_moments,

@@ -1,0 +1,155 @@
+"""Local and non-local blocks of the retarded Green's function (`Hamiltonian.green`).
+
+G(z) = (z - H)^-1 at z = ε + iΓ for the whole 4N x 4N BdG matrix, Nambu basis (e↑, e↓, h↑, h↓) per site.
+`GreenFunction.blocks[t, k]` = G(E_k + iΓ_k)[4j_t:4j_t+4, 4i:4i+4] for the source site i and the target
+sites j_t.  The helpers are slices of these blocks, so no sign convention is hidden in them.
+
+Route: the unit vectors e_{4i+b} of the source site run through the Chebyshev recurrence on
+the GPU, and every step stores the rows of the target sites (`bdg_green_moments`): the moments
+μ_n[ja, ib] = <e_{4j+a}|T_n(H/a)|e_{4i+b}>.  The blocks follow from the operator form of
+`chebyshev.resolvent_series`,
+
+    G(z)[ja, ib] = -i / (a·sqrt(1 - z̃²)) · Σ_n (2 - δ_n0) · exp(-i·n·arccos z̃) · μ_n[ja, ib],   z̃ = z/a.
+
+With particle-hole symmetry (H = -τx H* τx) only the electron columns b = 0, 1 are run; the hole columns are
+μ_n[a, b] = (-1)ⁿ·conj μ_n[a⊕2, b⊕2].  Probing several sources with one vector does not work here: G(ε + iΓ)
+decays far too slowly with distance, so every source site gets its own start vectors.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from .common import Coord
+
+HOST_TABLE_LIMIT = 1 << 30  # bytes of one call's moment table on the host: more targets go in groups
+
+
+def moment_weights(n_moments: int, scale: float, z: np.ndarray) -> np.ndarray:
+    """(len(z), n_moments) weights w[k, n] with G(z_k) = Σ_n w[k, n] μ_n, for Im z > 0."""
+    zt = np.asarray(z, dtype=np.complex128) / scale
+    angle = np.arccos(zt)
+    weights = np.exp(-1j * angle[:, None] * np.arange(n_moments)[None, :])
+    weights[:, 1:] *= 2.0
+    return weights * (-1j / (scale * np.sqrt(1 - zt * zt)))[:, None]
+
+
+def hole_columns(mu: np.ndarray) -> np.ndarray:
+    """(M, T, 4, 4) moments from the electron columns (M, T, 4, 2): μ_n[a, b] = (-1)ⁿ conj μ_n[a⊕2, b⊕2]."""
+    full = np.empty(mu.shape[:3] + (4,), dtype=np.complex128)
+    full[..., 0:2] = mu
+    sign = np.where(np.arange(mu.shape[0]) & 1, -1.0, 1.0)[:, None, None, None]
+    full[..., 2:4] = sign * mu[:, :, [2, 3, 0, 1], :].conj()
+    return full
+
+
+def blocks_from_moments(mu: np.ndarray, scale: float, z: np.ndarray) -> np.ndarray:
+    """(T, K, 4, 4) blocks G(z_k) from the moments (M, T, 4, 4)."""
+    return np.einsum("kn,ntab->tkab", moment_weights(mu.shape[0], scale, z), mu, optimize=True)
+
+
+def reference_broadening(energies: np.ndarray) -> np.ndarray:
+    """Γ per energy by the rule of `observables.ldos`: ε = unique(|E|), Γ = gradient(ε), E takes the Γ of |E|."""
+    eps = np.unique(np.abs(energies))
+    if eps.size < 2:
+        raise ValueError("green: the default broadening needs at least two distinct |energies| (or pass broadening=...)")
+    gam = np.gradient(eps)
+    return gam[np.searchsorted(eps, np.abs(energies))]
+
+
+class GreenFunction:
+    """Blocks of G(ε + iΓ) from one source site to the target sites.
+
+    `blocks` (T, K, 4, 4) complex128, `energies` and `broadening` (K,), `source` and `targets` lattice
+    coordinates, `info` the route details (moments, scale, perf record, whether the hole columns were derived).
+    """
+
+    def __init__(self, blocks: np.ndarray, energies: np.ndarray, broadening: np.ndarray, source: Coord, targets,
+                 info: dict | None = None):
+        self.blocks = blocks
+        self.energies = energies
+        self.broadening = broadening
+        self.source = tuple(source)
+        self.targets = [tuple(t) for t in targets]
+        self.info = dict(info or {})
+
+    def _local(self, t: int, name: str) -> np.ndarray:
+        if self.targets[t] != self.source:
+            raise ValueError(f"{name}: target {self.targets[t]} is not the source site {self.source} (a local quantity)")
+        return self.blocks[t]
+
+    def ldos(self, t: int = 0) -> np.ndarray:
+        """(K,) spin-summed electron LDOS -Im(G[0,0] + G[1,1])/π."""
+        g = self._local(t, "ldos")
+        return -(g[:, 0, 0] + g[:, 1, 1]).imag / np.pi
+
+    def spin_ldos(self, t: int = 0) -> np.ndarray:
+        """(K, 2) -Im G[0,0]/π and -Im G[1,1]/π."""
+        g = self._local(t, "spin_ldos")
+        return np.stack([-g[:, 0, 0].imag, -g[:, 1, 1].imag], axis=1) / np.pi
+
+    def spin_density(self, t: int = 0) -> np.ndarray:
+        """(K, 3) -Im tr(σ_k G[0:2, 0:2])/π for k = x, y, z."""
+        from .common import σ1, σ2, σ3
+
+        g = self._local(t, "spin_density")[:, 0:2, 0:2]
+        return np.stack([-np.einsum("ab,kba->k", s, g).imag for s in (σ1, σ2, σ3)], axis=1) / np.pi
+
+    def anomalous(self, t: int = 0) -> np.ndarray:
+        """(K, 2, 2) the electron-hole block G[0:2, 2:4]."""
+        return self.blocks[t][:, 0:2, 2:4].copy()
+
+
+def green(system, source: Coord, energies, targets=None, *, broadening=None, moments: int | None = None,
+          digits: float = 12.0, scale: float | None = None, _all_columns: bool = False) -> GreenFunction:
+    """G(E + iΓ) from `source` to `targets` (see `Hamiltonian.green`)."""
+    from . import chebyshev as cheb
+    from .observables import _scale_of
+
+    source = tuple(source)
+    targets = [source] if targets is None else [tuple(t) for t in targets]
+    if not targets:
+        raise ValueError("green: targets is empty")
+    energies = np.array(energies, dtype=float).reshape(-1)
+    if energies.size == 0:
+        raise ValueError("green: energies is empty")
+    if broadening is None:
+        gamma = reference_broadening(energies)
+    else:
+        gamma = np.asarray(broadening, dtype=float)
+        if gamma.ndim == 0:
+            gamma = np.full(energies.shape, float(gamma))
+        elif gamma.shape != energies.shape:
+            raise ValueError(f"green: broadening of shape {gamma.shape} for energies of shape {energies.shape}")
+    if not np.all(gamma > 0):
+        raise ValueError("green: the broadening must be positive")
+    scale = _scale_of(system) if scale is None else float(scale)
+    if np.any(np.abs(energies) >= scale):
+        raise ValueError(f"green: |energy| must stay below the spectral bound {scale:.6g}")
+    if moments is None:
+        moments = cheb.moments_for_resolvent(scale, float(np.min(gamma)), digits)
+    moments = int(moments)
+    if moments < 1:
+        raise ValueError("green: moments must be >= 1")
+
+    site = int(system.lattice[source])
+    target_sites = np.array([system.lattice[t] for t in targets], dtype=np.int64)
+    distinct, where = np.unique(target_sites, return_inverse=True)  # (a block row has one slot in the device table)
+    # particle-hole symmetry (H = -τx H* τx block by block) gives the hole columns from the electron columns
+    derive = not _all_columns and system.has_symmetric_spectrum(1e-12)
+    columns = 2 if derive else 4
+    rows = 4 * site + np.arange(columns, dtype=np.int64)
+
+    solver = system._solver()
+    z = energies + 1j * gamma
+    per_target = moments * 4 * columns * 16
+    group = max(1, HOST_TABLE_LIMIT // per_target)
+    blocks = np.empty((distinct.size, energies.size, 4, 4), dtype=np.complex128)
+    perf = []
+    for lo in range(0, distinct.size, group):
+        mu = solver.green_moments(scale, moments, rows, distinct[lo : lo + group])
+        perf.append(solver.perf())
+        blocks[lo : lo + group] = blocks_from_moments(hole_columns(mu) if derive else mu, scale, z)
+    info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+            "perf": perf[0] if len(perf) == 1 else perf}
+    return GreenFunction(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, source, targets, info)

@@ -501,6 +501,15 @@ class Hamiltonian:
 
         return fermi_matrix(self, temperature, **options)
 
+    def green(self, source: Coord, energies, targets=None, **options):
+        """Blocks of the retarded Green's function G(ε + iΓ) = (ε + iΓ - H)^-1 from the site `source` to the
+        sites `targets` (default: the source itself), as a `GreenFunction` with the slices ldos(),
+        spin_ldos(), spin_density(), anomalous().  Not part of the reference API; options (broadening,
+        moments, digits, scale) are those of `bodge_amd.green.green`."""
+        from .green import green
+
+        return green(self, source, energies, targets, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

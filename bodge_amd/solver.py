@@ -224,6 +224,20 @@ class DeviceSolver:
             int(n_components), backend.as_i32p(indptr), backend.as_i32p(indices), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def green_moments(self, scale, n_moments, source_rows, target_block_rows) -> np.ndarray:
+        """(n_moments, n_targets, 4, n_sources) complex moments <e_{4j+a}|T_n(H/scale)|e_row> for the scalar rows
+        `source_rows` and the distinct block rows j of `target_block_rows` (bdg_green_moments)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        source_rows = np.ascontiguousarray(source_rows, dtype=np.int64).reshape(-1)
+        target_block_rows = np.ascontiguousarray(target_block_rows, dtype=np.int32).reshape(-1)
+        if int(n_moments) < 1 or source_rows.size < 1 or target_block_rows.size < 1:
+            raise ValueError("green_moments: expected at least one moment, one source row and one target block row")
+        out = np.empty((int(n_moments), target_block_rows.size, 4, source_rows.size), dtype=np.complex128)
+        backend.check(self._lib.bdg_green_moments(
+            self._handle, float(scale), int(n_moments), source_rows.size, backend.as_i64p(source_rows),
+            target_block_rows.size, backend.as_i32p(target_block_rows), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def lanczos_begin(self, n_vectors: int, seed: int = 0, first_id: int = 0, kind: int = VEC_RADEMACHER,
                       max_iter: int = 10000) -> None:
         """Start n_vectors independent Lanczos processes on H^2 (see `lanczos_advance`)."""

@@ -35,6 +35,10 @@ rho = system.ldos((L // 2, L // 2, 0), energies)
 print(f"ldos at the centre, 13 energies [{time.perf_counter() - t0:.2f} s]:", np.round(rho, 4))
 
 t0 = time.perf_counter()
+g = system.green((L // 2, L // 2, 0), energies)
+print(f"green at the centre, spin-resolved ldos [{time.perf_counter() - t0:.2f} s]:", np.round(g.spin_ldos().T, 4))
+
+t0 = time.perf_counter()
 print(f"excitation gap = {system.lowest_eigenvalues(1)[0]:.6f}   [{time.perf_counter() - t0:.2f} s]")
 
 if 4 * L * L <= 2048:

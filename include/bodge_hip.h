@@ -89,6 +89,9 @@ typedef struct bdg_perf {
     int32_t groups_per_launch; /* lane groups (batches of the call) advanced by one persistent launch, else 1 */
     int32_t clenshaw;      /* bdg_fermi_blocks: 1 = its Clenshaw steps ran the streamed-block kernel (cheb_clenshaw),
                               2 = the dictionary kernel (cheb_clenshaw_dict); 0 = the call was another one */
+    int32_t green;         /* bdg_green_moments: 1 = its picked steps ran the streamed-block kernel (cheb_green),
+                              2 = the dictionary kernel (cheb_green_dict); 0 = the call was another one */
+    int32_t green_ranges;  /* bdg_green_moments: ranges of moments the device table was filled and copied out in */
 } bdg_perf;
 
 const char* bdg_last_error(void);
@@ -185,6 +188,20 @@ int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_mo
 int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const double* coef, int32_t n_colours,
                      const int32_t* site_colour, int32_t n_components, const int32_t* pat_indptr,
                      const int32_t* pat_indices, double* blocks_out);
+
+/*
+ * Off-diagonal Chebyshev moments for the Green's function blocks G_ji:
+ *   out[(((n*n_targets + t)*4 + a)*n_sources + v)*2 + {0, 1}] = (re, im) of <e_{4j_t + a}|T_n(H/scale)|e_{source_rows[v]}>
+ * for n < n_moments, j_t = target_block_rows[t] (distinct block rows), a < 4.  Every source row is a unit
+ * start vector of the recurrence t_{n+1} = 2 H t_n / scale - t_{n-1}; one launch per moment advances the
+ * vectors and stores the rows of the target sites (kernels cheb_green / cheb_green_dict, no dot products).
+ * The source rows are batched by the width rule of the one-step kernels and run on the handle's stream.  On
+ * the device the table covers a range of moments of at most 256 MB (BODGE_AMD_GREEN_TABLE_BYTES) that is
+ * copied into `out` when it is full, so device memory does not grow with n_moments.  bdg_perf_query reports
+ * the call (`green` says which kernel form ran).  Whole matrices only (not slabs).
+ */
+int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,
+                      int32_t n_targets, const int32_t* target_block_rows, double* out);
 
 /* Per-start-vector moments for unit vectors: mu_out[m*n_vectors + r]. */
 int bdg_cheb_diag_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_vectors,
