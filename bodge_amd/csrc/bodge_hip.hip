@@ -60,6 +60,7 @@
 #include "recurrence.hpp"
 #include "fermi.hpp"
 #include "green.hpp"
+#include "green_map.hpp"
 #include "lanczos.hpp"
 #include "dense.hpp"
 #include "tridiag.hpp"
@@ -666,6 +667,11 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
 int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,
                       int32_t n_targets, const int32_t* target_block_rows, double* out) {
     return run_green_moments(sys, scale, n_moments, n_sources, source_rows, n_targets, target_block_rows, out);
+}
+
+int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
+                            const int32_t* block_rows, int32_t n_components, double* out) {
+    return run_green_local_moments(sys, scale, n_moments, n_sites, block_rows, n_components, out);
 }
 
 int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_moments,

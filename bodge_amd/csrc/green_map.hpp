@@ -1,47 +1,56 @@
-// green.hpp - off-diagonal Chebyshev moments <e_{4j+a}|T_n(H~)|e_{4i+b}> for the Green's function blocks G_ji
-// (bdg_green_moments).  Part of the single translation unit bodge_hip.hip (included after fermi.hpp): the
-// kernels live in namespace bdg beside the Clenshaw kernels, the driver in the unnamed namespace.
+// green_map.hpp - local Chebyshev moments <e_{4j+a}|T_n(H~)|e_{4j+b}> at many sites j per batch, for the local
+// Green's function blocks G_jj (bdg_green_local_moments).  Part of the single translation unit bodge_hip.hip
+// (included after green.hpp): the kernels live in namespace bdg beside the picked kernels of green(), the
+// driver in the unnamed namespace.
 //
-// Picked recurrence.  A unit start vector e_{4i+b} run through t_{n+1} = 2 H~ t_n - t_{n-1}
-// (H~ = H / scale) holds T_n(H~) e_{4i+b}; the four entries of t_n on the rows of a target site j are the
-// moments mu_n[ja, ib].  A picked step moves what a recurrence step moves plus one int32 per block row (the
-// target slot, -1 on all rows but the targets'), forms no dot product, and on a target row stores the four
-// components of every active vector into the moment table.  Every table entry has one writer.
+// Full-width picked recurrence.  A batch carries the unit start vectors of up to 64 / C sites
+// (C = 2 or 4 Nambu columns per site): vector v = C * s + b starts at e_{4 j_s + b}.  Every vector runs the
+// recurrence of green.hpp on its own; of t_n only the four entries on the rows of the vector's OWN site are
+// moments that anybody wants.  So on the block row of slot s only the C vectors that belong to s store, 64 B
+// each: table [n - n0][s][a][b].  One writer per entry, no atomics, no reduction, and the table grows with
+// the number of sites, not with its square as the S x 2S product of bdg_green_moments would.
 #pragma once
 
 namespace bdg {
 
-// What a picked launch reads besides a recurrence step's arguments.  table is the slice of this launch's
-// moment: double2 (re, im) [n_targets][4][n_active]; vectors from n_active on are padding and stay zero.
-struct GreenArgs {
-    StepArgs s;               // matrix, vector buffers, tiles; partial / discard / col_* are not read
-    const int* target_slot;   // [nb] slot of the block row in the table, -1 = not a target
+// What a launch reads besides a recurrence step's arguments.  table is the slice of this launch's moment:
+// double2 (re, im) [n_slots][4][1 << comp_shift].  site_slot holds the position of a block row in the CALL's
+// site list (one upload per call); the batch owns the positions slot_base .. slot_base + n_slots - 1.
+struct GreenLocalArgs {
+    StepArgs s;             // matrix, vector buffers, tiles; partial / discard / col_* are not read
+    const int* site_slot;   // [nb] position of the block row in the site list, -1 = not a mapped site
     double2* table;
-    int n_active;
+    int slot_base;
+    int n_slots;
+    int comp_shift;         // log2 of the columns per site: 1 or 2
 };
 
-// The four rows of block row `slot`'s site, vectors of lane payload r.  PER_LANE = 1: nx[al] is the complex
-// entry of vector r; 2: .x / .y are the real entries of vectors 2r, 2r+1, unpacked into (value, 0).
+// The four rows of a mapped site, vectors of lane payload r: stored only by the vectors that start on this
+// site (v - (slot << comp_shift) is a column).  PER_LANE as in store_picked: 2 = .x / .y are the real entries of vectors
+// 2r, 2r+1, unpacked into (value, 0).
 template <int PER_LANE>
-__device__ inline void store_picked(const GreenArgs& g, int slot, int r, const double2 nx[4]) {
-    if (slot < 0) return;
+__device__ inline void store_local(const GreenLocalArgs& g, int position, int r, const double2 nx[4]) {
+    const int slot = position - g.slot_base;  // (position -1: negative as well)
+    if (slot < 0 || slot >= g.n_slots) return;
+    // (everything below hangs on the slot just loaded: nothing of it can be kept in registers across the tile loop)
+    double2* site = g.table + ((slot * 4) << g.comp_shift);
 #pragma unroll
     for (int q = 0; q < PER_LANE; ++q) {
-        const int v = PER_LANE * r + q;
-        if (v < g.n_active) {
+        const int b = PER_LANE * r + q - (slot << g.comp_shift);  // column of vector v = PER_LANE * r + q on this site
+        if (b >= 0 && b < (1 << g.comp_shift)) {
 #pragma unroll
             for (int al = 0; al < 4; ++al) {
                 const double2 value = PER_LANE == 2 ? make_double2(q == 0 ? nx[al].x : nx[al].y, 0.0) : nx[al];
-                g.table[((size_t)slot * 4 + al) * g.n_active + v] = value;
+                site[(al << g.comp_shift) + b] = value;
             }
         }
     }
 }
 
-// Generic form: cheb_clenshaw's tile loop (LDS staging of the streamed blocks, gathers of t_n) with the
-// epilogue t_{n+1} = coef * (H t_n) - t_{n-1} and the store of the target rows.
+// Generic form: the twin of cheb_green (LDS staging of the streamed blocks, gathers of t_n, epilogue
+// t_{n+1} = coef * (H t_n) - t_{n-1}) with the store of the vectors' own rows.
 template <typename Mode, int RL>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green(GreenArgs ga) {
+__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_local(GreenLocalArgs ga) {
     extern __shared__ double2 lds[];
     const StepArgs& a = ga.s;
     constexpr int RW = kWave / RL;
@@ -124,8 +133,6 @@ __global__ __launch_bounds__(kBlockThreads, 4) void cheb_green(GreenArgs ga) {
         }
 
         if (valid) {
-            // (read here, not before the tile loop: one live register less across it keeps ComplexPHMode out of scratch)
-            const int target = ga.target_slot[i];
             double2 nx[4];
 #pragma unroll
             for (int al = 0; al < 4; ++al) {
@@ -140,15 +147,16 @@ __global__ __launch_bounds__(kBlockThreads, 4) void cheb_green(GreenArgs ga) {
                 if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
                 else a.prev[own] = nx[al];
             }
-            store_picked<Mode::kVec>(ga, target, r, nx);
+            // (the position is read here, after the tile loop and the vector stores: nothing of it is live before)
+            store_local<Mode::kVec>(ga, ga.site_slot[i], r, nx);
         }
     }
 }
 
-// Dictionary form: cheb_clenshaw_dict's tile loop (block table in LDS, fixed-width row words, own and
+// Dictionary form: the twin of cheb_green_dict (block table in LDS, fixed-width row words, own and
 // neighbouring rows of t_n shared through LDS) with the same epilogue.
 template <typename Mode, int RL, int MAXB>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_dict(GreenArgs ga) {
+__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_local_dict(GreenLocalArgs ga) {
     extern __shared__ double2 lds[];
     const StepArgs& a = ga.s;
     constexpr int RW = kWave / RL;
@@ -233,7 +241,6 @@ __global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_dict(GreenArgs ga
                 const long ss = (long)s + d;
                 return (ss >= 0 && ss < RW && (long)i + d < a.nb) ? (int)d : (int)kWave;
             };
-            const int target = ga.target_slot[i];
             double2 acc[4], x[4], xn[4];
 #pragma unroll
             for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
@@ -281,7 +288,8 @@ __global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_dict(GreenArgs ga
 #pragma unroll
                 for (int al = 0; al < 4; ++al) a.prev[vslot(al, (size_t)i, r, a.ncols, RL)] = p[al];
             }
-            store_picked<Mode::kVec>(ga, target, r, p);
+            // (the position is read in the epilogue, not before the tile's products: one live register less across them)
+            store_local<Mode::kVec>(ga, ga.site_slot[i], r, p);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_wave_barrier();
@@ -290,18 +298,20 @@ __global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_dict(GreenArgs ga
     }
 }
 
-// Moment 0 from the start vectors themselves: table[slot][al][v] = t_0[al][target_rows[slot]][v].  One thread
-// per entry.  PER_LANE = 2: real payloads, vector v in component v & 1 of payload v >> 1.
+// Moment 0 from the start vectors themselves: table[s][al][b] = t_0[al][rows[s]][(s << comp_shift) + b], with
+// the vector index counted inside the batch.  One thread per entry.  PER_LANE = 2: real payloads, vector v in
+// component v & 1 of payload v >> 1.
 template <int PER_LANE>
-__global__ void green_pick(const double2* __restrict__ vec, int64_t nb, int rl, const int* __restrict__ target_rows,
-                           int n_targets, int n_active, double2* __restrict__ table) {
-    const int64_t total = (int64_t)n_targets * 4 * n_active;
+__global__ void green_local_pick(const double2* __restrict__ vec, int64_t nb, int rl, const int* __restrict__ rows,
+                                 int n_slots, int comp_shift, double2* __restrict__ table) {
+    const int64_t total = ((int64_t)n_slots * 4) << comp_shift;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (int64_t)gridDim.x * blockDim.x) {
-        const int v = (int)(idx % n_active);
-        const int al = (int)((idx / n_active) & 3);
-        const int64_t slot = idx / (4 * (int64_t)n_active);
-        const double2 pair = vec[vslot(al, (size_t)target_rows[slot], v / PER_LANE, (size_t)nb, rl)];
+        const int b = (int)(idx & ((1 << comp_shift) - 1));
+        const int al = (int)((idx >> comp_shift) & 3);
+        const int64_t slot = idx >> (comp_shift + 2);
+        const int v = (int)(slot << comp_shift) + b;
+        const double2 pair = vec[vslot(al, (size_t)rows[slot], v / PER_LANE, (size_t)nb, rl)];
         table[idx] = PER_LANE == 2 ? make_double2((v & 1) ? pair.y : pair.x, 0.0) : pair;
     }
 }
@@ -310,122 +320,72 @@ __global__ void green_pick(const double2* __restrict__ vec, int64_t nb, int rl, 
 
 namespace {
 
-using GreenKernel = void (*)(bdg::GreenArgs);
+using GreenLocalKernel = void (*)(bdg::GreenLocalArgs);
 
 template <typename Mode>
-GreenKernel green_generic_for(int rl) {
+GreenLocalKernel green_local_generic_for(int rl) {
     switch (rl) {
-        case 4: return bdg::cheb_green<Mode, 4>;
-        case 8: return bdg::cheb_green<Mode, 8>;
-        case 16: return bdg::cheb_green<Mode, 16>;
-        case 32: return bdg::cheb_green<Mode, 32>;
-        case 64: return bdg::cheb_green<Mode, 64>;
+        case 4: return bdg::cheb_green_local<Mode, 4>;
+        case 8: return bdg::cheb_green_local<Mode, 8>;
+        case 16: return bdg::cheb_green_local<Mode, 16>;
+        case 32: return bdg::cheb_green_local<Mode, 32>;
+        case 64: return bdg::cheb_green_local<Mode, 64>;
     }
     return nullptr;
 }
 
 template <typename Mode, int MAXB>
-GreenKernel green_dict_for(int rl) {
+GreenLocalKernel green_local_dict_for(int rl) {
     switch (rl) {
-        case 4: return bdg::cheb_green_dict<Mode, 4, MAXB>;
-        case 8: return bdg::cheb_green_dict<Mode, 8, MAXB>;
-        case 16: return bdg::cheb_green_dict<Mode, 16, MAXB>;
-        case 32: return bdg::cheb_green_dict<Mode, 32, MAXB>;
+        case 4: return bdg::cheb_green_local_dict<Mode, 4, MAXB>;
+        case 8: return bdg::cheb_green_local_dict<Mode, 8, MAXB>;
+        case 16: return bdg::cheb_green_local_dict<Mode, 16, MAXB>;
+        case 32: return bdg::cheb_green_local_dict<Mode, 32, MAXB>;
     }
     // (64 lanes: complex modes only, as for the Clenshaw dictionary kernel)
     if constexpr (Mode::kVec == 1)
-        if (rl == 64) return bdg::cheb_green_dict<Mode, 64, MAXB>;
+        if (rl == 64) return bdg::cheb_green_local_dict<Mode, 64, MAXB>;
     return nullptr;
 }
 
 template <typename Mode>
-GreenKernel green_kernel_for(bool dictionary, int max_row_blocks, int rl) {
-    if (!dictionary) return green_generic_for<Mode>(rl);
-    if (max_row_blocks <= 3) return green_dict_for<Mode, 3>(rl);
-    if (max_row_blocks <= 5) return green_dict_for<Mode, 5>(rl);
-    return green_dict_for<Mode, 7>(rl);
+GreenLocalKernel green_local_kernel_for(bool dictionary, int max_row_blocks, int rl) {
+    if (!dictionary) return green_local_generic_for<Mode>(rl);
+    if (max_row_blocks <= 3) return green_local_dict_for<Mode, 3>(rl);
+    if (max_row_blocks <= 5) return green_local_dict_for<Mode, 5>(rl);
+    return green_local_dict_for<Mode, 7>(rl);
 }
 
-GreenKernel green_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
+GreenLocalKernel green_local_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
     switch (mode.id) {
-        case 1: return green_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
-        case 2: return green_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
-        case 3: return green_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
+        case 1: return green_local_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
+        case 2: return green_local_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
+        case 3: return green_local_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
     }
-    return green_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
+    return green_local_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
 }
 
-// Launch plan of a picked step: that of the Clenshaw kernels (make_clenshaw_plan) for the kernel that
-// `select(mode, dictionary, max_row_blocks, rl)` names (the kernels of this file, or those of green_map.hpp).
-template <typename Kernel>
-struct PickedPlan {
-    StepPlan step;  // tiles, grid, LDS, mode, dictionary flag (step.kernel unused)
-    Kernel kernel = nullptr;
-};
-using GreenPlan = PickedPlan<GreenKernel>;
-
-template <typename Kernel, typename Select>
-int make_picked_plan(bdg_system* sys, int rl, const ModeInfo& mode, Select select, PickedPlan<Kernel>* out) {
-    StepPlan& plan = out->step;
-    plan = StepPlan{};
-    plan.rl = rl;
-    plan.mode = mode;
-    const int rows_per_wave = bdg::kWave / rl;
-    plan.rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
-    plan.n_tiles = (int)((sys->nb + plan.rows_per_tile - 1) / plan.rows_per_tile);
-    plan.dictionary = dict_kernel(sys, mode, rl) != nullptr;
-    out->kernel = select(mode, plan.dictionary, sys->max_row_blocks, rl);
-    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the picked recurrence kernels", rl);
-    if (plan.dictionary) {
-        plan.lds_bytes = plan.lds_footprint = (size_t)sys->n_unique * mode.stride * sizeof(double2) +
-                                              (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
-    } else {
-        const int tile_blocks = rows_per_wave * std::max(1, sys->max_row_blocks);
-        const int cap = (int)((160 * 1024 / bdg::kWavesPerBlock) / (mode.stride * sizeof(double2)));
-        plan.stage_blocks = std::max(1, std::min(tile_blocks, cap));
-        plan.lds_bytes = plan.lds_footprint =
-            (size_t)bdg::kWavesPerBlock * plan.stage_blocks * mode.stride * sizeof(double2);
-        if (plan.lds_bytes > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(out->kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
-    }
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(out->kernel),
-                                                         bdg::kBlockThreads, plan.lds_bytes));
-    per_cu = std::max(1, std::min(per_cu, 8));
-    if (const char* cap = knob::raw("BODGE_AMD_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(cap));
-    const int grid = std::min(plan.n_tiles, per_cu * sys->num_cus);
-    plan.grid = std::max(8, (grid + 7) / 8 * 8);
-    return BDG_OK;
-}
-
-int make_green_plan(bdg_system* sys, int rl, const ModeInfo& mode, GreenPlan* out) {
-    return make_picked_plan(sys, rl, mode, green_kernel, out);
-}
-
-constexpr size_t kGreenTableBytes = (size_t)256 << 20;  // device moment table: a range of moments at a time
-
-int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_sources, const int64_t* source_rows,
-                      int n_targets, const int32_t* target_block_rows, double* out) {
+int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_sites, const int32_t* block_rows,
+                            int n_components, double* out) {
     if (!sys) return fail(BDG_EINVAL, "null system handle");
-    if (!source_rows || !target_block_rows || !out) return fail(BDG_EINVAL, "null argument");
+    if (!block_rows || !out) return fail(BDG_EINVAL, "null argument");
     if (sys->ncols != sys->nb || sys->row_offset != 0)
-        return fail(BDG_EINVAL, "bdg_green_moments needs a whole (square) matrix: slabs are not supported");
+        return fail(BDG_EINVAL, "bdg_green_local_moments needs a whole (square) matrix: slabs are not supported");
     if (!(scale > 0.0)) return fail(BDG_EINVAL, "scale must be positive");
     if (n_moments < 1) return fail(BDG_EINVAL, "n_moments must be >= 1");
-    if (n_sources < 1) return fail(BDG_EINVAL, "n_sources must be >= 1");
-    if (n_targets < 1) return fail(BDG_EINVAL, "n_targets must be >= 1");
+    if (n_sites < 1) return fail(BDG_EINVAL, "n_sites must be >= 1");
+    if (n_components != 2 && n_components != 4) return fail(BDG_EINVAL, "n_components must be 2 or 4");
     const int64_t nb = sys->nb;
-    for (int v = 0; v < n_sources; ++v)
-        if (source_rows[v] < 0 || source_rows[v] >= 4 * nb)
-            return fail(BDG_EINVAL, "source row %lld out of range", (long long)source_rows[v]);
-    // slot of every block row in the table; a block row is listed once (one writer per table entry)
-    std::vector<int32_t> slot_of((size_t)nb, -1);
-    for (int t = 0; t < n_targets; ++t) {
-        const int32_t j = target_block_rows[t];
-        if (j < 0 || j >= nb) return fail(BDG_EINVAL, "target block row %d out of range", j);
-        if (slot_of[(size_t)j] >= 0) return fail(BDG_EINVAL, "target block row %d is listed twice", j);
-        slot_of[(size_t)j] = t;
+    const int comp_shift = n_components == 2 ? 1 : 2;
+    // position of every block row in the site list; a block row is listed once (one writer per table entry)
+    std::vector<int32_t> position((size_t)nb, -1);
+    std::vector<int64_t> start_rows((size_t)n_sites * n_components);
+    for (int s = 0; s < n_sites; ++s) {
+        const int32_t j = block_rows[s];
+        if (j < 0 || j >= nb) return fail(BDG_EINVAL, "block row %d out of range", j);
+        if (position[(size_t)j] >= 0) return fail(BDG_EINVAL, "block row %d is listed twice", j);
+        position[(size_t)j] = s;
+        for (int b = 0; b < n_components; ++b) start_rows[(size_t)s * n_components + b] = 4 * (int64_t)j + b;
     }
     lanczos_free(sys);
     HIP_TRY(hipSetDevice(sys->device));
@@ -436,18 +396,19 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
     const char* ph_env = knob::raw("BODGE_AMD_PH");
     const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
     const int per_lane = mode.per_lane;
-    // Source rows per batch: the widest power of two up to 64 whose vector buffer stays within 96 MB
-    // (batch_width's rule for the one-step kernels); set_lanes_per_row fixes the lanes instead.
+    // Vectors per batch: the widest power of two up to 64 whose vector buffer stays within 96 MB (batch_width's
+    // rule for the one-step kernels); set_lanes_per_row fixes the lanes instead.  A batch holds whole sites.
     const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
     int width = 64;
     while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
     if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
-    width = std::min(width, n_sources);
+    width = std::min(width, n_sites * n_components);
     int rl = std::max(4, next_pow2((width + per_lane - 1) / per_lane));
     if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= width) rl = sys->lanes_override;
     const int rv = rl * per_lane;
-    GreenPlan gplan;
-    if (int rc = make_green_plan(sys, rl, mode, &gplan)) return rc;
+    const int batch_sites = width / n_components;
+    PickedPlan<GreenLocalKernel> gplan;
+    if (int rc = make_picked_plan(sys, rl, mode, green_local_kernel, &gplan)) return rc;
     const StepPlan& plan = gplan.step;
     bdg::StepArgs base{};
     if (int rc = matrix_args(sys, plan, &base)) return rc;
@@ -460,53 +421,57 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
     if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
     bool alternate = true;
     if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
-    const int n_batches = (n_sources + width - 1) / width;
+    const int n_batches = (n_sites + batch_sites - 1) / batch_sites;
 
-    // Device table: [moment of the range][target][component][vector of the batch]; a range of moments whose
+    // Device table: [moment of the range][site of the batch][component][column]; a range of moments whose
     // entries fit the limit, copied into the caller's table when it is full.
     size_t limit = kGreenTableBytes;
     if (const char* env = knob::raw("BODGE_AMD_GREEN_TABLE_BYTES")) limit = (size_t)std::max(1LL, atoll(env));
-    const size_t per_moment_max = (size_t)n_targets * 4 * (size_t)width;  // double2 entries of one moment
+    const size_t per_site = (size_t)4 * n_components;                   // double2 entries of one site and moment
+    const size_t per_moment_max = (size_t)batch_sites * per_site;
     const int range = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moments, limit / (per_moment_max * sizeof(double2))));
     const int n_ranges = (n_moments + range - 1) / range;
 
     if (int rc = sys->vec_a.reserve(vec_count)) return rc;
     if (int rc = sys->vec_b.reserve(vec_count)) return rc;
-    DeviceBuffer<int> d_slot, d_targets;
+    DeviceBuffer<int> d_position, d_sites;
     DeviceBuffer<int64_t> d_rows;
     DeviceBuffer<double2> d_table;
     std::vector<hipEvent_t> events;
     auto body = [&]() -> int {
-        if (int rc = d_slot.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
-        if (int rc = d_targets.reserve((size_t)n_targets)) return rc;
-        if (int rc = d_rows.reserve((size_t)n_sources)) return rc;
+        if (int rc = d_position.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
+        if (int rc = d_sites.reserve((size_t)n_sites)) return rc;
+        if (int rc = d_rows.reserve(start_rows.size())) return rc;
         if (int rc = d_table.reserve((size_t)range * per_moment_max)) return rc;
         hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_slot.ptr, slot_of.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_targets.ptr, target_block_rows, sizeof(int) * n_targets, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_rows.ptr, source_rows, sizeof(int64_t) * n_sources, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_position.ptr, position.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_sites.ptr, block_rows, sizeof(int) * n_sites, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_rows.ptr, start_rows.data(), sizeof(int64_t) * start_rows.size(), hipMemcpyHostToDevice, st));
         events.assign((size_t)2 * n_batches * n_ranges, nullptr);
         for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
 
         const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
         bdg_perf perf{};
         for (int b = 0; b < n_batches; ++b) {
-            const int v0 = b * width;
-            const int n_active = std::min(width, n_sources - v0);
-            const size_t per_moment = (size_t)n_targets * 4 * (size_t)n_active;
-            bdg::GreenArgs ga{};
+            const int s0 = b * batch_sites;
+            const int n_slots = std::min(batch_sites, n_sites - s0);
+            const int n_active = n_slots * n_components;
+            const size_t per_moment = (size_t)n_slots * per_site;
+            bdg::GreenLocalArgs ga{};
             ga.s = base;
-            ga.target_slot = d_slot.ptr;
-            ga.n_active = n_active;
+            ga.site_slot = d_position.ptr;
+            ga.slot_base = s0;
+            ga.n_slots = n_slots;
+            ga.comp_shift = comp_shift;
             double2* cur = sys->vec_a.ptr;
             double2* prev = sys->vec_b.ptr;
             bdg::fill_zero<<<fill_grid, 256, 0, st>>>(cur, (int64_t)vec_count);
             bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
+            const int64_t* rows = d_rows.ptr + (size_t)s0 * n_components;
             if (real)
-                bdg::set_unit_real<<<1, 64, 0, st>>>(reinterpret_cast<double*>(cur), nb, nb, rv, n_active,
-                                                     d_rows.ptr + v0, (int64_t)0);
+                bdg::set_unit_real<<<1, 64, 0, st>>>(reinterpret_cast<double*>(cur), nb, nb, rv, n_active, rows, (int64_t)0);
             else
-                bdg::set_unit<<<1, 64, 0, st>>>(cur, nb, nb, rv, n_active, d_rows.ptr + v0, (int64_t)0);
+                bdg::set_unit<<<1, 64, 0, st>>>(cur, nb, nb, rv, n_active, rows, (int64_t)0);
             for (int g = 0; g < n_ranges; ++g) {
                 const int n0 = g * range, n1 = std::min(n_moments, n0 + range);
                 const size_t ev = (size_t)2 * (b * n_ranges + g);
@@ -517,9 +482,9 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
                         // mu_0 from t_0 itself
                         const int grid = (int)std::min<size_t>(1024, (per_moment + 255) / 256);
                         if (real)
-                            bdg::green_pick<2><<<grid, 256, 0, st>>>(cur, nb, rl, d_targets.ptr, n_targets, n_active, slice);
+                            bdg::green_local_pick<2><<<grid, 256, 0, st>>>(cur, nb, rl, d_sites.ptr + s0, n_slots, comp_shift, slice);
                         else
-                            bdg::green_pick<1><<<grid, 256, 0, st>>>(cur, nb, rl, d_targets.ptr, n_targets, n_active, slice);
+                            bdg::green_local_pick<1><<<grid, 256, 0, st>>>(cur, nb, rl, d_sites.ptr + s0, n_slots, comp_shift, slice);
                         continue;
                     }
                     // t_1 = H~ t_0 (t_{-1} = 0), then t_{n+1} = 2 H~ t_n - t_{n-1}: the new vector replaces prev
@@ -533,15 +498,15 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
                 }
                 HIP_TRY(hipEventRecord(events[ev + 1], st));
                 HIP_TRY(hipGetLastError());
-                // rows (moment, target, component) of n_active entries into the caller's rows of n_sources
-                double2* dst = reinterpret_cast<double2*>(out) + (size_t)n0 * n_targets * 4 * (size_t)n_sources + v0;
-                if (n_active == n_sources)
+                // rows (moment) of the batch's n_slots sites into the caller's rows of n_sites sites
+                double2* dst = reinterpret_cast<double2*>(out) + ((size_t)n0 * n_sites + s0) * per_site;
+                if (n_slots == n_sites)
                     HIP_TRY(hipMemcpyAsync(dst, d_table.ptr, sizeof(double2) * (size_t)(n1 - n0) * per_moment,
                                            hipMemcpyDeviceToHost, st));
                 else
-                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double2) * (size_t)n_sources, d_table.ptr,
-                                             sizeof(double2) * (size_t)n_active, sizeof(double2) * (size_t)n_active,
-                                             (size_t)(n1 - n0) * n_targets * 4, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double2) * (size_t)n_sites * per_site, d_table.ptr,
+                                             sizeof(double2) * per_moment, sizeof(double2) * per_moment,
+                                             (size_t)(n1 - n0), hipMemcpyDeviceToHost, st));
             }
             perf.vector_steps += (int64_t)(n_moments - 1) * n_active;
         }
@@ -571,8 +536,8 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
         perf.dict_skipped = sys->dict_skipped;
         perf.streams = 1;
         perf.groups_per_launch = 1;
-        perf.green = plan.dictionary ? 2 : 1;
         perf.green_ranges = n_ranges;
+        perf.green_local = plan.dictionary ? 2 : 1;
         sys->perf = perf;
         return BDG_OK;
     };
@@ -580,8 +545,8 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
     if (rc) (void)hipStreamSynchronize(sys->stream);
     for (hipEvent_t ev : events)
         if (ev) (void)hipEventDestroy(ev);
-    d_slot.release();
-    d_targets.release();
+    d_position.release();
+    d_sites.release();
     d_rows.release();
     d_table.release();
     return rc;

@@ -59,7 +59,7 @@
 //   bdg_fermi_blocks (fermi.hpp) has no switch of its own: it follows DICT, REAL, PH, STREAMS, STREAM_VECTORS, ALTERNATE,
 //   BLOCKS_PER_CU and L2_BUDGET as the one-step kernels do, and bdg_set_lanes_per_row fixes its batch width.  Its
 //   four-column form (no particle-hole halving, for tests) is the private keyword `_all_columns` of fermi_matrix.
-//   bdg_green_moments (green.hpp) follows DICT, REAL, PH, STREAM_VECTORS, ALTERNATE, BLOCKS_PER_CU and L2_BUDGET likewise, and
+//   bdg_green_moments (green.hpp) and bdg_green_local_moments (green_map.hpp) follow DICT, REAL, PH, STREAM_VECTORS, ALTERNATE, BLOCKS_PER_CU and L2_BUDGET likewise, and
 //     BODGE_AMD_GREEN_TABLE_BYTES=bytes      limit of its device moment table (default 256 MB): a call whose table is larger
 //                                            fills and copies out one range of moments after the other (tests lower it)
 #pragma once

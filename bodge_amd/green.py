@@ -1,4 +1,4 @@
-"""Local and non-local blocks of the retarded Green's function (`Hamiltonian.green`).
+"""Local and non-local blocks of the retarded Green's function (`Hamiltonian.green`, `Hamiltonian.green_map`).
 
 G(z) = (z - H)^-1 at z = ε + iΓ for the whole 4N x 4N BdG matrix, Nambu basis (e↑, e↓, h↑, h↓) per site.
 `GreenFunction.blocks[t, k]` = G(E_k + iΓ_k)[4j_t:4j_t+4, 4i:4i+4] for the source site i and the target
@@ -14,6 +14,11 @@ the GPU, and every step stores the rows of the target sites (`bdg_green_moments`
 With particle-hole symmetry (H = -τx H* τx) only the electron columns b = 0, 1 are run; the hole columns are
 μ_n[a, b] = (-1)ⁿ·conj μ_n[a⊕2, b⊕2].  Probing several sources with one vector does not work here: G(ε + iΓ)
 decays far too slowly with distance, so every source site gets its own start vectors.
+
+Maps: `green_map` wants the local block G_jj at many sites j.  The start vectors of up to 32
+sites share one batch of the recurrence, and a step stores for every vector the rows of its own site only
+(`bdg_green_local_moments`), so a launch runs at full width and the moment table grows with the number of
+sites, not with its square.
 """
 
 from __future__ import annotations
@@ -55,6 +60,36 @@ def reference_broadening(energies: np.ndarray) -> np.ndarray:
         raise ValueError("green: the default broadening needs at least two distinct |energies| (or pass broadening=...)")
     gam = np.gradient(eps)
     return gam[np.searchsorted(eps, np.abs(energies))]
+
+
+def _series_arguments(system, energies, broadening, moments, digits, scale):
+    """Energies, Γ per energy, moments and scale of a call, checked (the rules of `green`)."""
+    from . import chebyshev as cheb
+    from .observables import _scale_of
+
+    energies = np.array(energies, dtype=float).reshape(-1)
+    if energies.size == 0:
+        raise ValueError("green: energies is empty")
+    if broadening is None:
+        gamma = reference_broadening(energies)
+    else:
+        gamma = np.asarray(broadening, dtype=float)
+        if gamma.ndim == 0:
+            gamma = np.full(energies.shape, float(gamma))
+        elif gamma.shape != energies.shape:
+            raise ValueError(f"green: broadening of shape {gamma.shape} for energies of shape {energies.shape}")
+    if not np.all(gamma > 0):
+        raise ValueError("green: the broadening must be positive")
+    scale = _scale_of(system) if scale is None else float(scale)
+    if np.any(np.abs(energies) >= scale):
+        raise ValueError(f"green: |energy| must stay below the spectral bound {scale:.6g}")
+    if moments is None:
+        moments = cheb.moments_for_resolvent(scale, float(np.min(gamma)), digits)
+    moments = int(moments)
+    if moments < 1:
+        raise ValueError("green: moments must be >= 1")
+
+    return energies, gamma, moments, scale
 
 
 class GreenFunction:
@@ -103,34 +138,11 @@ class GreenFunction:
 def green(system, source: Coord, energies, targets=None, *, broadening=None, moments: int | None = None,
           digits: float = 12.0, scale: float | None = None, _all_columns: bool = False) -> GreenFunction:
     """G(E + iΓ) from `source` to `targets` (see `Hamiltonian.green`)."""
-    from . import chebyshev as cheb
-    from .observables import _scale_of
-
     source = tuple(source)
     targets = [source] if targets is None else [tuple(t) for t in targets]
     if not targets:
         raise ValueError("green: targets is empty")
-    energies = np.array(energies, dtype=float).reshape(-1)
-    if energies.size == 0:
-        raise ValueError("green: energies is empty")
-    if broadening is None:
-        gamma = reference_broadening(energies)
-    else:
-        gamma = np.asarray(broadening, dtype=float)
-        if gamma.ndim == 0:
-            gamma = np.full(energies.shape, float(gamma))
-        elif gamma.shape != energies.shape:
-            raise ValueError(f"green: broadening of shape {gamma.shape} for energies of shape {energies.shape}")
-    if not np.all(gamma > 0):
-        raise ValueError("green: the broadening must be positive")
-    scale = _scale_of(system) if scale is None else float(scale)
-    if np.any(np.abs(energies) >= scale):
-        raise ValueError(f"green: |energy| must stay below the spectral bound {scale:.6g}")
-    if moments is None:
-        moments = cheb.moments_for_resolvent(scale, float(np.min(gamma)), digits)
-    moments = int(moments)
-    if moments < 1:
-        raise ValueError("green: moments must be >= 1")
+    energies, gamma, moments, scale = _series_arguments(system, energies, broadening, moments, digits, scale)
 
     site = int(system.lattice[source])
     target_sites = np.array([system.lattice[t] for t in targets], dtype=np.int64)
@@ -153,3 +165,81 @@ def green(system, source: Coord, energies, targets=None, *, broadening=None, mom
     info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
             "perf": perf[0] if len(perf) == 1 else perf}
     return GreenFunction(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, source, targets, info)
+
+
+class GreenMap:
+    """Local blocks of G(ε + iΓ) at many sites.
+
+    `blocks` (S, K, 4, 4) complex128: blocks[s, k] = G(E_k + iΓ_k)[4j_s:4j_s+4, 4j_s:4j_s+4]; `energies` and
+    `broadening` (K,), `sites` the lattice coordinates, `info` the route details as in `GreenFunction`.  The
+    helpers are those of `GreenFunction` with one leading site axis more.
+    """
+
+    def __init__(self, blocks: np.ndarray, energies: np.ndarray, broadening: np.ndarray, sites, info: dict | None = None):
+        self.blocks = blocks
+        self.energies = energies
+        self.broadening = broadening
+        self.sites = [tuple(site) for site in sites]
+        self.info = dict(info or {})
+
+    def site(self, coord: Coord) -> np.ndarray:
+        """(K, 4, 4) blocks of the site `coord` (its first position in `sites`)."""
+        coord = tuple(coord)
+        if coord not in self.sites:
+            raise ValueError(f"site: {coord} is not among the mapped sites")
+        return self.blocks[self.sites.index(coord)]
+
+    def ldos(self) -> np.ndarray:
+        """(S, K) spin-summed electron LDOS -Im(G[0,0] + G[1,1])/π."""
+        g = self.blocks
+        return -(g[:, :, 0, 0] + g[:, :, 1, 1]).imag / np.pi
+
+    def spin_ldos(self) -> np.ndarray:
+        """(S, K, 2) -Im G[0,0]/π and -Im G[1,1]/π."""
+        g = self.blocks
+        return np.stack([-g[:, :, 0, 0].imag, -g[:, :, 1, 1].imag], axis=2) / np.pi
+
+    def spin_density(self) -> np.ndarray:
+        """(S, K, 3) -Im tr(σ_k G[0:2, 0:2])/π for k = x, y, z."""
+        from .common import σ1, σ2, σ3
+
+        g = self.blocks[:, :, 0:2, 0:2]
+        return np.stack([-np.einsum("ab,skba->sk", s, g).imag for s in (σ1, σ2, σ3)], axis=2) / np.pi
+
+    def anomalous(self) -> np.ndarray:
+        """(S, K, 2, 2) the electron-hole blocks G[0:2, 2:4]."""
+        return self.blocks[:, :, 0:2, 2:4].copy()
+
+
+def green_map(system, energies, sites=None, *, broadening=None, moments: int | None = None, digits: float = 12.0,
+              scale: float | None = None, _all_columns: bool = False) -> GreenMap:
+    """Local blocks G_jj(E + iΓ) at the sites `sites` (see `Hamiltonian.green_map`)."""
+    if sites is None:
+        sites = list(system.lattice.sites())
+        indices = np.arange(system.lattice.size, dtype=np.int64)
+    else:
+        sites = [tuple(site) for site in sites]
+        indices = np.array([system.lattice[site] for site in sites], dtype=np.int64)
+    if not sites:
+        raise ValueError("green: sites is empty")
+    energies, gamma, moments, scale = _series_arguments(system, energies, broadening, moments, digits, scale)
+
+    distinct, where = np.unique(indices, return_inverse=True)  # (a block row is listed once in a device call)
+    derive = not _all_columns and system.has_symmetric_spectrum(1e-12)
+    columns = 2 if derive else 4
+
+    solver = system._solver()
+    z = energies + 1j * gamma
+    per_site = moments * 4 * columns * 16
+    group = max(1, HOST_TABLE_LIMIT // per_site)
+    if group > 64:
+        group -= group % 64  # (whole device batches: a batch holds 64 / columns sites or a power of two less)
+    blocks = np.empty((distinct.size, energies.size, 4, 4), dtype=np.complex128)
+    perf = []
+    for lo in range(0, distinct.size, group):
+        mu = solver.green_local_moments(scale, moments, distinct[lo : lo + group], columns)
+        perf.append(solver.perf())
+        blocks[lo : lo + group] = blocks_from_moments(hole_columns(mu) if derive else mu, scale, z)
+    info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+            "perf": perf[0] if len(perf) == 1 else perf}
+    return GreenMap(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, sites, info)

@@ -510,6 +510,15 @@ class Hamiltonian:
 
         return green(self, source, energies, targets, **options)
 
+    def green_map(self, energies, sites=None, **options):
+        """Local blocks G_jj(ε + iΓ) of the retarded Green's function at the sites `sites` (default: every
+        site in index order), as a `GreenMap` whose slices ldos(), spin_ldos(), spin_density(), anomalous()
+        carry a leading site axis: LDOS line cuts and maps from full-width batches of the recurrence.  Not
+        part of the reference API; options (broadening, moments, digits, scale) are those of `green`."""
+        from .green import green_map
+
+        return green_map(self, energies, sites, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

@@ -238,6 +238,19 @@ class DeviceSolver:
             target_block_rows.size, backend.as_i32p(target_block_rows), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def green_local_moments(self, scale, n_moments, block_rows, n_components: int = 4) -> np.ndarray:
+        """(n_moments, n_sites, 4, n_components) complex moments <e_{4j+a}|T_n(H/scale)|e_{4j+b}> on the distinct
+        block rows j of `block_rows`, many sites per batch (bdg_green_local_moments)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        block_rows = np.ascontiguousarray(block_rows, dtype=np.int32).reshape(-1)
+        if int(n_moments) < 1 or block_rows.size < 1 or int(n_components) not in (2, 4):
+            raise ValueError("green_local_moments: expected at least one moment, one block row and 2 or 4 components")
+        out = np.empty((int(n_moments), block_rows.size, 4, int(n_components)), dtype=np.complex128)
+        backend.check(self._lib.bdg_green_local_moments(
+            self._handle, float(scale), int(n_moments), block_rows.size, backend.as_i32p(block_rows),
+            int(n_components), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def lanczos_begin(self, n_vectors: int, seed: int = 0, first_id: int = 0, kind: int = VEC_RADEMACHER,
                       max_iter: int = 10000) -> None:
         """Start n_vectors independent Lanczos processes on H^2 (see `lanczos_advance`)."""

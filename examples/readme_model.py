@@ -39,6 +39,10 @@ g = system.green((L // 2, L // 2, 0), energies)
 print(f"green at the centre, spin-resolved ldos [{time.perf_counter() - t0:.2f} s]:", np.round(g.spin_ldos().T, 4))
 
 t0 = time.perf_counter()
+cut = system.green_map(energies, [(x, L // 2, 0) for x in range(L)])
+print(f"green_map along y = L/2, ldos at E = 0 [{time.perf_counter() - t0:.2f} s]:", np.round(cut.ldos()[:, 6], 4))
+
+t0 = time.perf_counter()
 print(f"excitation gap = {system.lowest_eigenvalues(1)[0]:.6f}   [{time.perf_counter() - t0:.2f} s]")
 
 if 4 * L * L <= 2048:

@@ -91,7 +91,10 @@ typedef struct bdg_perf {
                               2 = the dictionary kernel (cheb_clenshaw_dict); 0 = the call was another one */
     int32_t green;         /* bdg_green_moments: 1 = its picked steps ran the streamed-block kernel (cheb_green),
                               2 = the dictionary kernel (cheb_green_dict); 0 = the call was another one */
-    int32_t green_ranges;  /* bdg_green_moments: ranges of moments the device table was filled and copied out in */
+    int32_t green_ranges;  /* bdg_green_moments, bdg_green_local_moments: ranges of moments the device table was
+                              filled and copied out in */
+    int32_t green_local;   /* bdg_green_local_moments: 1 = its steps ran the streamed-block kernel (cheb_green_local),
+                              2 = the dictionary kernel (cheb_green_local_dict); 0 = the call was another one */
 } bdg_perf;
 
 const char* bdg_last_error(void);
@@ -202,6 +205,21 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
  */
 int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,
                       int32_t n_targets, const int32_t* target_block_rows, double* out);
+
+/*
+ * Local Chebyshev moments at many sites per batch, for maps of the local Green's function blocks G_jj
+ * (DESIGN.md §12):
+ *   out[(((n*n_sites + s)*4 + a)*n_components + b)*2 + {0, 1}] = (re, im) of <e_{4j_s + a}|T_n(H/scale)|e_{4j_s + b}>
+ * for n < n_moments, j_s = block_rows[s] (distinct block rows), a < 4, b < n_components (2: the electron
+ * columns, 4: all).  The unit vectors of up to 64 / n_components sites share one batch of the one-step width
+ * rule (bdg_set_lanes_per_row fixes the lanes); one launch per moment advances all of them, and on the rows
+ * of a site only the vectors that started there store (kernels cheb_green_local / cheb_green_local_dict: one
+ * writer per entry, no dot products).  The device table covers a range of moments of at most 256 MB
+ * (BODGE_AMD_GREEN_TABLE_BYTES), copied into `out` when it is full.  bdg_perf_query reports the call
+ * (`green_local` says which kernel form ran).  Whole matrices only (not slabs).
+ */
+int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
+                            const int32_t* block_rows, int32_t n_components, double* out);
 
 /* Per-start-vector moments for unit vectors: mu_out[m*n_vectors + r]. */
 int bdg_cheb_diag_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_vectors,
