@@ -56,6 +56,7 @@ class Perf(C.Structure):
         ("green", C.c_int32),
         ("green_ranges", C.c_int32),
         ("green_local", C.c_int32),
+        ("apply", C.c_int32),
     ]
 
 
@@ -92,6 +93,7 @@ SIGNATURES = {
         C.c_int,
         [_handle, C.c_double, C.c_int32, _f64p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _f64p],
     ),
+    "bdg_apply_series": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p, _f64p]),
     "bdg_green_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, C.c_int32, _i32p, _f64p]),
     "bdg_green_local_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32, _f64p]),
     "bdg_cheb_diag_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p]),

@@ -93,6 +93,24 @@ def chebyshev_coefficients(func, n_moments: int, oversample: int = 4) -> np.ndar
     return coeff
 
 
+def chebyshev_coefficients_complex(func, n_moments: int, oversample: int = 4) -> np.ndarray:
+    """`chebyshev_coefficients` for a function that may be complex-valued: complex128 coefficients, the same
+    quadrature applied to the real and the imaginary part (the cosine transform is real-linear; scipy's dct of a
+    complex array is not relied on).  For a real-valued `func` the real parts are `chebyshev_coefficients`' numbers."""
+    from scipy.fft import dct
+
+    nodes = oversample * n_moments
+    theta = np.pi * (np.arange(nodes) + 0.5) / nodes
+    values = np.asarray(func(np.cos(theta)), dtype=np.complex128)
+    if values.shape != (nodes,):
+        raise ValueError("the function must map an array of energies to an array of the same shape")
+    coeff = np.empty(n_moments, dtype=np.complex128)
+    coeff.real = dct(np.ascontiguousarray(values.real), type=2)[:n_moments] / nodes
+    coeff.imag = dct(np.ascontiguousarray(values.imag), type=2)[:n_moments] / nodes
+    coeff[0] *= 0.5
+    return coeff
+
+
 def dots_to_moments(d: np.ndarray, e: np.ndarray) -> np.ndarray:
     """(steps, R) recurrence dots -> (2*steps, R) moments: μ_2n = 2 d_n - μ_0, μ_2n+1 = 2 e_n - μ_1."""
     mu = np.empty((2 * d.shape[0],) + d.shape[1:])

@@ -83,6 +83,9 @@ _CHECKS = {
     "int": lambda v: isinstance(v, numbers.Integral) and not isinstance(v, bool),
     "int | None": lambda v: v is None
     or (isinstance(v, numbers.Integral) and not isinstance(v, bool)),
+    "float | int": lambda v: isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_)),
+    "float | int | None": lambda v: v is None
+    or (isinstance(v, numbers.Real) and not isinstance(v, (bool, np.bool_))),
 }
 
 

@@ -59,6 +59,7 @@
 #include "libraries.hpp"
 #include "recurrence.hpp"
 #include "fermi.hpp"
+#include "apply.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
 #include "lanczos.hpp"
@@ -662,6 +663,11 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
                      const int32_t* pat_indices, double* blocks_out) {
     return run_fermi_blocks(sys, scale, n_moments, coef, n_colours, site_colour, n_components, pat_indptr, pat_indices,
                             blocks_out);
+}
+
+int bdg_apply_series(bdg_system* sys, double scale, int32_t n_moments, int32_t n_functions, const double* coef,
+                     int32_t n_vectors, const double* x, double* y_out) {
+    return run_apply_series(sys, scale, n_moments, n_functions, coef, n_vectors, x, y_out);
 }
 
 int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,

@@ -384,38 +384,47 @@ struct ClenshawPlan {
     ClenshawKernel kernel = nullptr;
 };
 
-int make_clenshaw_plan(bdg_system* sys, int rl, const ModeInfo& mode, ClenshawPlan* out) {
-    StepPlan& plan = out->step;
-    plan = StepPlan{};
-    plan.rl = rl;
-    plan.mode = mode;
+// The two halves of that plan, shared with the stored-source kernels of apply.hpp: the shape (tiles, form) that the
+// kernel lookup needs, then LDS and grid for the kernel found.
+void clenshaw_plan_shape(const bdg_system* sys, int rl, const ModeInfo& mode, StepPlan* plan) {
+    *plan = StepPlan{};
+    plan->rl = rl;
+    plan->mode = mode;
     const int rows_per_wave = bdg::kWave / rl;
-    plan.rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
-    plan.n_tiles = (int)((sys->nb + plan.rows_per_tile - 1) / plan.rows_per_tile);
-    plan.dictionary = dict_kernel(sys, mode, rl) != nullptr;
-    out->kernel = clenshaw_kernel(mode, plan.dictionary, sys->max_row_blocks, rl);
-    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the Clenshaw kernels", rl);
-    if (plan.dictionary) {
-        plan.lds_bytes = plan.lds_footprint = (size_t)sys->n_unique * mode.stride * sizeof(double2) +
-                                              (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
+    plan->rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
+    plan->n_tiles = (int)((sys->nb + plan->rows_per_tile - 1) / plan->rows_per_tile);
+    plan->dictionary = dict_kernel(sys, mode, rl) != nullptr;
+}
+
+int clenshaw_plan_launch(const bdg_system* sys, const void* kernel, StepPlan* plan) {
+    const ModeInfo& mode = plan->mode;
+    const int rows_per_wave = bdg::kWave / plan->rl;
+    if (plan->dictionary) {
+        plan->lds_bytes = plan->lds_footprint = (size_t)sys->n_unique * mode.stride * sizeof(double2) +
+                                                (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
     } else {
         const int tile_blocks = rows_per_wave * std::max(1, sys->max_row_blocks);
         const int cap = (int)((160 * 1024 / bdg::kWavesPerBlock) / (mode.stride * sizeof(double2)));
-        plan.stage_blocks = std::max(1, std::min(tile_blocks, cap));
-        plan.lds_bytes = plan.lds_footprint =
-            (size_t)bdg::kWavesPerBlock * plan.stage_blocks * mode.stride * sizeof(double2);
-        if (plan.lds_bytes > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(out->kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+        plan->stage_blocks = std::max(1, std::min(tile_blocks, cap));
+        plan->lds_bytes = plan->lds_footprint =
+            (size_t)bdg::kWavesPerBlock * plan->stage_blocks * mode.stride * sizeof(double2);
+        if (plan->lds_bytes > 64 * 1024)
+            HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan->lds_bytes));
     }
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(out->kernel),
-                                                         bdg::kBlockThreads, plan.lds_bytes));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, bdg::kBlockThreads, plan->lds_bytes));
     per_cu = std::max(1, std::min(per_cu, 8));
     if (const char* cap = knob::raw("BODGE_AMD_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(cap));
-    const int grid = std::min(plan.n_tiles, per_cu * sys->num_cus);
-    plan.grid = std::max(8, (grid + 7) / 8 * 8);
+    const int grid = std::min(plan->n_tiles, per_cu * sys->num_cus);
+    plan->grid = std::max(8, (grid + 7) / 8 * 8);
     return BDG_OK;
+}
+
+int make_clenshaw_plan(bdg_system* sys, int rl, const ModeInfo& mode, ClenshawPlan* out) {
+    clenshaw_plan_shape(sys, rl, mode, &out->step);
+    out->kernel = clenshaw_kernel(mode, out->step.dictionary, sys->max_row_blocks, rl);
+    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the Clenshaw kernels", rl);
+    return clenshaw_plan_launch(sys, reinterpret_cast<const void*>(out->kernel), &out->step);
 }
 
 // HBM bytes of one Clenshaw launch: a recurrence launch's (same matrix stream, same three vector passes)

@@ -519,6 +519,23 @@ class Hamiltonian:
 
         return green_map(self, energies, sites, **options)
 
+    def apply(self, function, vectors, **options):
+        """f(H) X for caller-supplied state vectors: `function` is a vectorised callable on real energies (it may be
+        complex-valued), or None with `coefficients=` giving the Chebyshev series on [-scale, scale] directly.
+        `vectors` in the layouts of `diagonalize` ((4N,), (4N, R), (N, 4) or (R, N, 4)); the result has the same
+        layout.  Not part of the reference API; options (coefficients, moments, digits, scale) are those of
+        `bodge_amd.apply.apply`."""
+        from .apply import apply
+
+        return apply(self, function, vectors, **options)
+
+    def evolve(self, vectors, times, **options):
+        """exp(-iHt) ψ for a scalar or an array of times (a leading time axis then), `vectors` as in `apply`.  Not
+        part of the reference API; options (digits, scale) are those of `bodge_amd.apply.evolve`."""
+        from .apply import evolve
+
+        return evolve(self, vectors, times, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

@@ -224,6 +224,22 @@ class DeviceSolver:
             int(n_components), backend.as_i32p(indptr), backend.as_i32p(indices), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def apply_series(self, scale, coef, x) -> np.ndarray:
+        """(V, F, 4N) complex y[v, f] = Σ_k coef[k, f] T_k(H/scale) x[v] for coefficients (M, F) and vectors (V, 4N),
+        both complex, by Clenshaw's recurrence with a stored source on the device (bdg_apply_series)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        coef = np.ascontiguousarray(coef, dtype=np.complex128)
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        if coef.ndim != 2 or coef.shape[0] < 1 or coef.shape[1] < 1:
+            raise ValueError("apply_series: expected coefficients of shape (moments, functions)")
+        if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] != self.dim:
+            raise ValueError(f"apply_series: expected vectors of shape (count, {self.dim})")
+        out = np.empty((x.shape[0], coef.shape[1], self.dim), dtype=np.complex128)
+        backend.check(self._lib.bdg_apply_series(
+            self._handle, float(scale), coef.shape[0], coef.shape[1], backend.as_f64p(coef.view(np.float64)),
+            x.shape[0], backend.as_f64p(x.view(np.float64)), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def green_moments(self, scale, n_moments, source_rows, target_block_rows) -> np.ndarray:
         """(n_moments, n_targets, 4, n_sources) complex moments <e_{4j+a}|T_n(H/scale)|e_row> for the scalar rows
         `source_rows` and the distinct block rows j of `target_block_rows` (bdg_green_moments)."""

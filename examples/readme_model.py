@@ -43,6 +43,17 @@ cut = system.green_map(energies, [(x, L // 2, 0) for x in range(L)])
 print(f"green_map along y = L/2, ldos at E = 0 [{time.perf_counter() - t0:.2f} s]:", np.round(cut.ldos()[:, 6], 4))
 
 t0 = time.perf_counter()
+E1, v1 = system.lowest_eigenpairs(1)
+t1 = time.perf_counter()
+times = np.linspace(0.0, 50.0, 6)
+moved = system.evolve(v1[0], times)  # an eigenstate only turns its phase: norm and energy stay
+h = system.matrix("csr")
+norms = np.linalg.norm(moved.reshape(len(times), -1), axis=1)
+energy = np.array([np.vdot(m.reshape(-1), h @ m.reshape(-1)).real for m in moved])
+print(f"lowest eigenstate E = {E1[0]:.6f} [{t1 - t0:.2f} s], evolved to t = 50 [{time.perf_counter() - t1:.2f} s]: "
+      f"norm drift {np.abs(norms - 1).max():.1e}, energy drift {np.abs(energy - energy[0]).max():.1e}")
+
+t0 = time.perf_counter()
 print(f"excitation gap = {system.lowest_eigenvalues(1)[0]:.6f}   [{time.perf_counter() - t0:.2f} s]")
 
 if 4 * L * L <= 2048:

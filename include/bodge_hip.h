@@ -95,6 +95,9 @@ typedef struct bdg_perf {
                               filled and copied out in */
     int32_t green_local;   /* bdg_green_local_moments: 1 = its steps ran the streamed-block kernel (cheb_green_local),
                               2 = the dictionary kernel (cheb_green_local_dict); 0 = the call was another one */
+    int32_t apply;         /* bdg_apply_series: 1 = its stored-source Clenshaw steps ran the streamed-block kernel
+                              (cheb_clenshaw_vec), 2 = the dictionary kernel (cheb_clenshaw_vec_dict); 0 = the call was
+                              another one */
 } bdg_perf;
 
 const char* bdg_last_error(void);
@@ -191,6 +194,25 @@ int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_mo
 int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const double* coef, int32_t n_colours,
                      const int32_t* site_colour, int32_t n_components, const int32_t* pat_indptr,
                      const int32_t* pat_indices, double* blocks_out);
+
+/*
+ * A Chebyshev series of H applied to caller-supplied vectors:
+ *   y[v, f] = sum_k coef[k, f] T_k(H/scale) x_v,   k < n_moments, f < n_functions, v < n_vectors
+ * coef[(k*n_functions + f)*2 + {0, 1}] = (re, im) of the complex coefficient c_k of function f (c_0 as it enters
+ * the sum, not doubled); x holds n_vectors vectors of 4*nb complex entries one after the other (site-major, the
+ * order of bdg_spmv); y_out + (v*n_functions + f)*8*nb receives the 4*nb complex entries of y[v, f].  The pairs
+ * (v, f) are the columns of Clenshaw's recurrence with a stored source, b_k = 2 H b_{k+1}/scale - b_{k+2} +
+ * c_k[f] x_v, one launch per coefficient (kernels cheb_clenshaw_vec / cheb_clenshaw_vec_dict, no dot products).
+ * A real matrix runs in real arithmetic with complex vectors and coefficients all the same: the two slots of a
+ * real kernel's lane payload carry Re and Im of one column.  Columns are batched by the width rule of the
+ * one-step kernels (one vector buffer within 96 MB, at most 64 columns, 32 in real arithmetic;
+ * bdg_set_lanes_per_row fixes the lanes = columns per batch) on the handle's stream sets.  bdg_perf_query
+ * reports the call: `apply` says which kernel form ran, vectors_per_launch counts a column of real arithmetic
+ * as two vectors (as bytes_per_launch does), vector_steps counts columns, and window_ms spans the batches'
+ * transfers between rounds when there are more batches than streams.  Whole matrices only (not slabs).
+ */
+int bdg_apply_series(bdg_system* sys, double scale, int32_t n_moments, int32_t n_functions, const double* coef,
+                     int32_t n_vectors, const double* x, double* y_out);
 
 /*
  * Off-diagonal Chebyshev moments for the Green's function blocks G_ji:
