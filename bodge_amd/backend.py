@@ -57,7 +57,16 @@ class Perf(C.Structure):
         ("green_ranges", C.c_int32),
         ("green_local", C.c_int32),
         ("apply", C.c_int32),
+        ("correlation", C.c_int32),
+        ("gram_ms", C.c_double),
+        ("gram_flops", C.c_double),
     ]
+
+
+class Operator(C.Structure):
+    """`bdg_operator`: a BSR operator with its own pattern (4x4 complex128 blocks, scipy BSR order)."""
+
+    _fields_ = [("nnzb", C.c_int32), ("indptr", _i32p), ("indices", _i32p), ("data", _f64p)]
 
 
 # name -> (restype, argtypes); every symbol declared in include/bodge_hip.h
@@ -94,6 +103,8 @@ SIGNATURES = {
         [_handle, C.c_double, C.c_int32, _f64p, C.c_int32, _i32p, C.c_int32, _i32p, _i32p, _f64p],
     ),
     "bdg_apply_series": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p, _f64p]),
+    "bdg_moment_matrix": (C.c_int, [_handle, C.c_double, C.c_int32, C.POINTER(Operator), C.POINTER(Operator), C.c_int32, _i64p,
+                                   _f64p, _f64p]),
     "bdg_green_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, C.c_int32, _i32p, _f64p]),
     "bdg_green_local_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32, _f64p]),
     "bdg_cheb_diag_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p]),

@@ -211,6 +211,36 @@ def moments_for_resolvent(scale: float, gamma: float, digits: float = 12.0) -> i
     return m + (m & 1)
 
 
+def moments_for_response(scale: float, temperature: float, broadening: float, digits: float = 12.0) -> int:
+    """Number M of Chebyshev moments per variable for the Kubo kernel (f(x) - f(y)) / (ω + iη + x - y) on [-a, a]².
+
+    Its nearest singularity sits at the distance γ = min(η, πT) from the band (the poles of the Fermi function at
+    ±iπT, the pole of the energy denominator at Im = η; η = 0 leaves πT); the Bernstein ellipse through it has
+    ln ρ = asinh(γ/a) and the coefficients decay like ρ^-m in either variable: M = ⌈digits·ln 10 / asinh(γ/a)⌉ + 16."""
+    if temperature <= 0:
+        raise ValueError("The Chebyshev expansion of the response needs T > 0")
+    if broadening < 0:
+        raise ValueError("The broadening must not be negative")
+    gamma = min(broadening, np.pi * temperature) if broadening > 0 else np.pi * temperature
+    m = int(np.ceil(digits * np.log(10.0) / np.arcsinh(gamma / scale))) + 16
+    return int(np.clip(m, 16, MAX_MOMENTS))
+
+
+def chebyshev_coefficients_2d(function, scale: float, n_moments: int) -> np.ndarray:
+    """(M, M) complex coefficients c_nm of F(x, y) ≈ Σ_nm c_nm T_n(x/scale) T_m(y/scale) on [-scale, scale]²: the
+    Chebyshev-Gauss rule of `chebyshev_coefficients` in both variables on 2M x 2M nodes, the c_0 row and column
+    halved.  `function` takes energies (not scaled) and broadcasts.  Two matrix products with a cosine table."""
+    nodes = 2 * n_moments
+    theta = np.pi * (np.arange(nodes) + 0.5) / nodes
+    energy = scale * np.cos(theta)
+    values = np.asarray(function(energy[:, None], energy[None, :]), dtype=np.complex128)
+    if values.shape != (nodes, nodes):
+        raise ValueError("the function must broadcast two arrays of energies to their common shape")
+    table = np.cos(np.arange(n_moments)[:, None] * theta[None, :]) * (2.0 / nodes)  # (M, nodes)
+    table[0] *= 0.5
+    return table @ values @ table.T
+
+
 def resolvent_series(mu: np.ndarray, scale: float, z: complex) -> complex:
     """<e|(z - H)^{-1}|e> given μ_n = <e|T_n(H/scale)|e>, for Im z > 0."""
     zt = complex(z) / scale

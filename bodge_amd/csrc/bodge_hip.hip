@@ -60,6 +60,7 @@
 #include "recurrence.hpp"
 #include "fermi.hpp"
 #include "apply.hpp"
+#include "correlation.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
 #include "lanczos.hpp"
@@ -668,6 +669,11 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
 int bdg_apply_series(bdg_system* sys, double scale, int32_t n_moments, int32_t n_functions, const double* coef,
                      int32_t n_vectors, const double* x, double* y_out) {
     return run_apply_series(sys, scale, n_moments, n_functions, coef, n_vectors, x, y_out);
+}
+
+int bdg_moment_matrix(bdg_system* sys, double scale, int32_t n_moments, const bdg_operator* a, const bdg_operator* b,
+                      int32_t n_vectors, const int64_t* rows, const double* x, double* mu_out) {
+    return run_moment_matrix(sys, scale, n_moments, a, b, n_vectors, rows, x, mu_out);
 }
 
 int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,

@@ -62,6 +62,12 @@
 //   bdg_green_moments (green.hpp) and bdg_green_local_moments (green_map.hpp) follow DICT, REAL, PH, STREAM_VECTORS, ALTERNATE, BLOCKS_PER_CU and L2_BUDGET likewise, and
 //     BODGE_AMD_GREEN_TABLE_BYTES=bytes      limit of its device moment table (default 256 MB): a call whose table is larger
 //                                            fills and copies out one range of moments after the other (tests lower it)
+//   bdg_moment_matrix (correlation.hpp) follows DICT, REAL, PH, STREAM_VECTORS, ALTERNATE, BLOCKS_PER_CU and L2_BUDGET as
+//   bdg_apply_series does (bdg_set_lanes_per_row fixes its batch width), and
+//     BODGE_AMD_CORRELATION_BYTES=bytes      limit of its two panels together (default 4 GiB): with fewer rows than moments
+//                                            the moments are blocked (tests lower it)
+//     BODGE_AMD_CORRELATION_SLICE=entries    complex entries of a panel row per workgroup of corr_gram (default 4096, a
+//                                            multiple of 4): fixes the summation order of a moment, whatever the blocking
 #pragma once
 
 #include <cstdlib>

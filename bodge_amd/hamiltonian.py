@@ -536,6 +536,17 @@ class Hamiltonian:
 
         return evolve(self, vectors, times, **options)
 
+    def correlation(self, A, B, **options):
+        """Double Chebyshev moments μ[n, m] = Tr[T_n(H~) A T_m(H~) B] of two operators (Hamiltonians on this lattice,
+        sparse or dense (4N, 4N) matrices, block arrays on this pattern; `bodge_amd.correlation.current_operator` and
+        `spin_operator` make the usual ones), as a `MomentMatrix` with expand(F), response(ω, T, η) and static(T): the
+        Kubo response Σ_ab A_ab B_ba F(E_a, E_b) without a diagonalisation.  Not part of the reference API; options
+        (moments, vectors, seed, scale, temperature, broadening, digits) are those of
+        `bodge_amd.correlation.correlation`."""
+        from .correlation import correlation
+
+        return correlation(self, A, B, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

@@ -240,6 +240,41 @@ class DeviceSolver:
             x.shape[0], backend.as_f64p(x.view(np.float64)), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def moment_matrix(self, scale, n_moments, a, b, rows=None, x=None) -> np.ndarray:
+        """(M, M) complex μ[n, m] = Σ_v <v|T_n(H/scale) A T_m(H/scale) B|v> (bdg_moment_matrix).  `a`, `b`: BSR triples
+        (indptr, indices, data (nnzb, 4, 4)) on this handle's block rows; the start vectors are the unit vectors of the
+        scalar rows `rows`, or the rows of `x` (V, 4N) - exactly one of the two."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        if (rows is None) == (x is None):
+            raise ValueError("moment_matrix: give exactly one of rows and x")
+        if int(n_moments) < 1:
+            raise ValueError("moment_matrix: expected at least one moment")
+        keep, operators = [], []
+        for name, (indptr, indices, data) in (("A", a), ("B", b)):
+            indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+            indices = np.ascontiguousarray(indices, dtype=np.int32)
+            data = np.ascontiguousarray(data, dtype=np.complex128)
+            if indptr.shape != (self.n_sites + 1,) or data.shape != (indices.size, 4, 4):
+                raise ValueError(f"moment_matrix: operator {name} does not describe the handle's {self.n_sites} block rows")
+            keep.append((indptr, indices, data))
+            operators.append(backend.Operator(indices.size, backend.as_i32p(indptr), backend.as_i32p(indices),
+                                              backend.as_f64p(data.view(np.float64))))
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+            count, rows_p, x_p = rows.size, backend.as_i64p(rows), None
+        else:
+            x = np.ascontiguousarray(x, dtype=np.complex128)
+            if x.ndim != 2 or x.shape[1] != self.dim:
+                raise ValueError(f"moment_matrix: expected vectors of shape (count, {self.dim})")
+            count, rows_p, x_p = x.shape[0], None, backend.as_f64p(x.view(np.float64))
+        if count < 1:
+            raise ValueError("moment_matrix: expected at least one start vector")
+        mu = np.empty((int(n_moments), int(n_moments)), dtype=np.complex128)
+        backend.check(self._lib.bdg_moment_matrix(
+            self._handle, float(scale), int(n_moments), C.byref(operators[0]), C.byref(operators[1]), count, rows_p, x_p,
+            backend.as_f64p(mu.view(np.float64))))
+        return mu
+
     def green_moments(self, scale, n_moments, source_rows, target_block_rows) -> np.ndarray:
         """(n_moments, n_targets, 4, n_sources) complex moments <e_{4j+a}|T_n(H/scale)|e_row> for the scalar rows
         `source_rows` and the distinct block rows j of `target_block_rows` (bdg_green_moments)."""

@@ -98,6 +98,10 @@ typedef struct bdg_perf {
     int32_t apply;         /* bdg_apply_series: 1 = its stored-source Clenshaw steps ran the streamed-block kernel
                               (cheb_clenshaw_vec), 2 = the dictionary kernel (cheb_clenshaw_vec_dict); 0 = the call was
                               another one */
+    int32_t correlation;   /* bdg_moment_matrix: 1 = the call was this one, 0 = another one */
+    double gram_ms;        /* bdg_moment_matrix: HIP-event time of its Gram + reduce launches (corr_gram, corr_reduce) */
+    double gram_flops;     /* bdg_moment_matrix: 8 x rows of X x rows of Y x K summed over the Gram launches, K = 4 nb x
+                              lanes_per_row complex entries per panel row */
 } bdg_perf;
 
 const char* bdg_last_error(void);
@@ -213,6 +217,40 @@ int bdg_fermi_blocks(bdg_system* sys, double scale, int32_t n_moments, const dou
  */
 int bdg_apply_series(bdg_system* sys, double scale, int32_t n_moments, int32_t n_functions, const double* coef,
                      int32_t n_vectors, const double* x, double* y_out);
+
+/* A BSR operator with its own pattern on the block rows of a system: indptr int32[nb + 1], indices int32[nnzb],
+ * data double[nnzb*32]: nnzb blocks of 4x4 complex128 in C order data[k][row][col] (re, im), scipy BSR order. */
+typedef struct bdg_operator {
+    int32_t nnzb;
+    const int32_t* indptr;
+    const int32_t* indices;
+    const double* data;
+} bdg_operator;
+
+/*
+ * Double Chebyshev moments of two operators:
+ *   mu_out[(n*n_moments + m)*2 + {0, 1}] = (re, im) of sum_v <v|T_n(H/scale) A T_m(H/scale) B|v>,   n, m < n_moments
+ * over n_vectors start vectors: the unit vectors e_{rows[v]} (rows index the 4*nb scalar rows), or the caller's
+ * vectors x (n_vectors vectors of 4*nb complex entries one after the other, site-major, the order of bdg_spmv);
+ * exactly one of rows / x is given, the other is NULL.  The start vectors are the columns of batches of the width
+ * rule of bdg_apply_series (bdg_set_lanes_per_row fixes the lanes = columns per batch).  Per batch two recurrences
+ * run on the handle's stream through the stored-source kernels of bdg_apply_series with a zero coefficient,
+ * X_n = T_n |r> and Y_m = A T_m B |r> (corr_operator applies A and B), into two panels of rows of
+ * K = 4*nb*lanes complex entries, and corr_gram (fp64 MFMA) forms P[s][n][m] = sum_{k in slice s} conj(X_n[k]) Y_m[k]
+ * on slices of BODGE_AMD_CORRELATION_SLICE entries (default 4096, a multiple of 4), which corr_reduce sums into mu in
+ * ascending order: no atomics, the same bits from run to run.  The panels hold Mb <= n_moments rows each, the
+ * largest multiple of 64 (or n_moments itself) for which both stay within BODGE_AMD_CORRELATION_BYTES (default
+ * 4 GiB); with Mb < n_moments the moments are blocked (Y once, chunk after chunk; X again for every chunk of Y), and
+ * a batch too wide for Mb = 64 is narrowed down to 4 lanes before the call gives up with BDG_EINVAL and the bytes
+ * needed.  Argument errors come before any device call, in this order: counts < 1, scale <= 0, null pointers, both
+ * or neither of rows / x, an operator with a negative count or null arrays, null handle, an operator whose
+ * indptr[nb] disagrees with its block count or whose indices leave [0, nb) (the matrix size comes from the
+ * handle), slab.  bdg_perf_query reports the call: correlation = 1, launches = recurrence launches (per batch and
+ * pass M - 1 steps of Y, and M of X: its restart from the kept start batch is one), vector_steps = columns x
+ * launches, gram_ms and gram_flops.  Whole matrices only (not slabs).
+ */
+int bdg_moment_matrix(bdg_system* sys, double scale, int32_t n_moments, const bdg_operator* a, const bdg_operator* b,
+                      int32_t n_vectors, const int64_t* rows, const double* x, double* mu_out);
 
 /*
  * Off-diagonal Chebyshev moments for the Green's function blocks G_ji:
