@@ -51,8 +51,10 @@ def _system(rng, case):
 
 
 def run(seed: int = 0, n_cases: int = 100, stages: str | None = None) -> int:
-    """`stages="2"`: the eigenvalues through the two-stage route (csrc/twostage.hpp: band by MFMA panels, bulge chasing) for every
-    real matrix large enough for a band (4N > 66) - the eigenvectors keep the one-stage route either way."""
+    """`stages="2"`: the two-stage route (csrc/twostage.hpp: band by MFMA panels, bulge chasing) for every real matrix large
+    enough for a band (4N > 66) - for the eigenvalues and for the eigenvectors of `eigh_above` alike: inverse iteration on the
+    band matrix, then the block reflectors of stage 1 (csrc/tridiag.hpp; BODGE_AMD_EIGH_BAND_VECTORS=0 would keep the one-stage
+    route for the vectors, and this script does not set it)."""
     rng = np.random.default_rng(seed)
     failures, t_start = 0, time.time()
     for case in range(n_cases):

@@ -6,6 +6,8 @@ import pytest
 
 import bodge_amd as ba
 
+from test_gpu_apply import ARITHMETIC
+
 pytestmark = pytest.mark.gpu
 
 ENERGIES = np.array([-0.4, -0.2, 0.0, 0.2, 0.4, 0.6, 0.8, 1.0, 0.2])  # both signs, unordered, one repeat
@@ -114,14 +116,12 @@ def relative_error(got, exact):
 # ------------------------------------------------------------------ against the dense inverse
 @pytest.mark.parametrize("name", sorted(SYSTEMS))
 @pytest.mark.parametrize("form", ["dictionary", "streamed"])
-@pytest.mark.parametrize("arithmetic", ["packed", "complex_full"])
+@pytest.mark.parametrize("arithmetic", sorted(ARITHMETIC))
 def test_blocks_match_the_dense_inverse(name, form, arithmetic, knobs):
     system = SYSTEMS[name]()
     if form == "streamed":
         knobs.set("BODGE_AMD_DICT", "0")
-    if arithmetic == "complex_full":
-        knobs.set("BODGE_AMD_REAL", "0")
-        knobs.set("BODGE_AMD_PH", "0")
+    knobs.update(ARITHMETIC[arithmetic])
     tolerance = min(20 * RESTATEMENT_ERROR[name], 1e-10)
     for broadening in (None, 0.05):
         g = system.green(SOURCE, ENERGIES, TARGETS, broadening=broadening)
@@ -139,9 +139,13 @@ def test_blocks_match_the_dense_inverse(name, form, arithmetic, knobs):
             assert perf["green"] == 1 and perf["dict_blocks"] == 0
         if arithmetic == "complex_full":
             assert perf["real_arithmetic"] == 0 and perf["ph_packed"] == 0
+        if arithmetic.startswith("complex"):
+            assert perf["real_arithmetic"] == 0
+        if arithmetic.endswith("full"):
+            assert perf["ph_packed"] == 0
     if form == "dictionary" and name in ("swave_zeeman", "dwave"):
         assert perf["green"] == 2 and perf["dict_blocks"] > 0
-    if arithmetic == "packed" and name in ("swave_zeeman", "dwave", "ssd"):
+    if arithmetic in ("packed", "real_full") and name in ("swave_zeeman", "dwave", "ssd"):
         assert perf["real_arithmetic"] == 1
 
 
