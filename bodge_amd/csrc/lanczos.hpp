@@ -103,6 +103,18 @@ int lanczos_begin(bdg_system* sys, int n_vectors, const StartSpec& start, int ma
     if (int rc = lanczos_norms(sys, lz, lz->w_cur, nullptr, false)) return rc;
     bdg::lanczos_scalars<<<1, 128, 0, sys->stream>>>(lz->z, lz->sums.ptr, lz->cols, 0, 0);
     HIP_TRY(hipGetLastError());
+    // which kernel form the run uses, as the Clenshaw drivers report it (launches: K1, counted per iteration)
+    bdg_perf perf{};
+    perf.lanes_per_row = b.rl;
+    perf.vectors_per_launch = b.rv;
+    perf.grid = b.plan.grid;
+    perf.lds_bytes = (int32_t)b.plan.lds_footprint;
+    perf.pipelined = 0;
+    perf.real_arithmetic = b.real ? 1 : 0;
+    perf.ph_packed = b.mode.ph ? 1 : 0;
+    perf.dict_blocks = b.plan.dictionary ? sys->n_unique : 0;
+    perf.steps_per_launch = 1;
+    sys->perf = perf;
     guard.keep = true;
     sys->lanczos = lz;
     return BDG_OK;
@@ -128,6 +140,7 @@ int lanczos_iterate(bdg_system* sys, LanczosState* lz, bdg::StepArgs& args, int 
     if (int rc = lanczos_norms(sys, lz, lz->w_prev, lz->w_cur, true)) return rc;
     bdg::lanczos_scalars<<<1, 128, 0, st>>>(lz->z, lz->sums.ptr, lz->cols, j + 1, 0);
     std::swap(lz->w_cur, lz->w_prev);
+    sys->perf.launches += 2;
     return BDG_OK;
 }
 

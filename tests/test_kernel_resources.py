@@ -96,3 +96,39 @@ def test_chunk_kernel_and_dense_two_stage_kernels_keep_their_registers(resources
     for name in ("ts_chase", "ts_band_vectors"):
         row = _row(resources, name)
         assert row["scratch"] == 0 and row["vgpr"] <= 256, (name, row)
+
+
+@pytest.mark.timeout(600)
+def test_lanczos_kernels_do_not_spill_and_keep_their_occupancy(resources):
+    """The kernels only the Lanczos process runs.  K1 with per-column scalars became compile-time variants because the
+    scalars once cost the dictionary kernel a spill: no instance may touch scratch, and an instance keeps
+    the occupancy its plain twin is pinned to above (dictionary form and generic complex form: four waves per SIMD).
+    Finding: the scalars cost every generic instance four VGPRs, and where the plain twin sits
+    at 126 - 128 that is one occupancy level - the generic complex form at 4 .. 32 lanes per row (130 VGPRs, three
+    waves; its twin is pinned to four), and, with twins that no test pins, RealMode and RealPHMode at 16 and 64 lanes
+    per row (130 - 132 VGPRs, three waves against four).  Those instances are pinned to the registers they have, so
+    that they do not get worse unnoticed; ComplexMode at 64 lanes per row keeps four waves."""
+    modes = ("RealPHMode", "ComplexPHMode", "RealMode", "ComplexMode")
+    for mode in modes:
+        for maxb in (3, 5, 7):
+            row = _row(resources, f"cheb_step_dict<bdg::{mode}, 4, {maxb}, true>")
+            assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, maxb, row)
+        for lanes in (4, 8, 16, 32, 64):
+            row = _row(resources, f"cheb_step<bdg::{mode}, {lanes}, true>")
+            assert row["scratch"] == 0 and row["vgpr"] <= 168 and row["occupancy"] >= 3, (mode, lanes, row)
+    for lanes in (4, 8, 16, 32):  # one occupancy level below cheb_step<ComplexMode, lanes, false>
+        row = _row(resources, f"cheb_step<bdg::ComplexMode, {lanes}, true>")
+        assert row["vgpr"] <= 130 and row["occupancy"] >= 3, (lanes, row)
+    for mode, lanes, vgpr in (("RealMode", 16, 132), ("RealMode", 64, 130), ("RealPHMode", 16, 132), ("RealPHMode", 64, 132)):
+        assert _row(resources, f"cheb_step<bdg::{mode}, {lanes}, false>")["occupancy"] >= 4  # (what the scalars cost)
+        row = _row(resources, f"cheb_step<bdg::{mode}, {lanes}, true>")
+        assert row["vgpr"] <= vgpr and row["occupancy"] >= 3, (mode, lanes, row)
+    row = _row(resources, "cheb_step<bdg::ComplexMode, 64, true>")
+    assert row["vgpr"] <= 128 and row["occupancy"] >= 4, row
+    for name in ("lanczos_combine", "column_norms", "lanczos_accumulate", "block_gram", "block_mix"):
+        for per_lane in (1, 2):
+            row = _row(resources, f"{name}<{per_lane}>")
+            assert row["scratch"] == 0, (name, per_lane, row)
+    # block_mix keeps a whole row of the block (16 payloads) and its result in registers: three / four waves
+    assert _row(resources, "block_mix<1>")["occupancy"] >= 3 and _row(resources, "block_mix<2>")["occupancy"] >= 4
+    assert _row(resources, "block_gram<1>")["occupancy"] >= 6 and _row(resources, "block_gram<2>")["occupancy"] >= 8
