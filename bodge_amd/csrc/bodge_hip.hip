@@ -63,6 +63,7 @@
 #include "correlation.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
+#include "green_states.hpp"
 #include "lanczos.hpp"
 #include "dense.hpp"
 #include "tridiag.hpp"
@@ -684,6 +685,11 @@ int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t 
 int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
                             const int32_t* block_rows, int32_t n_components, double* out) {
     return run_green_local_moments(sys, scale, n_moments, n_sites, block_rows, n_components, out);
+}
+
+int bdg_green_state_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_states,
+                            const double* amplitudes, int32_t n_components, double* out) {
+    return run_green_state_moments(sys, scale, n_moments, n_states, amplitudes, n_components, out);
 }
 
 int bdg_cheb_moments(bdg_system* sys, bdg_comm* comm, double scale, int32_t n_moments,

@@ -19,6 +19,13 @@ Maps: `green_map` wants the local block G_jj at many sites j.  
 sites share one batch of the recurrence, and a step stores for every vector the rows of its own site only
 (`bdg_green_local_moments`), so a launch runs at full width and the moment table grows with the number of
 sites, not with its square.
+
+Extended states: `green_states` wants <w a|G|w b> for a state w spread over the lattice, with
+|w b> = Σ_j w[j] e_{4j+b} - G(k, ε) for a plane wave (`spectral_function`).  The Nambu vectors of up to 64 / C
+states share one batch, and a step projects t_n on the states with conj(w) instead of picking rows
+(`bdg_green_state_moments`).  The hole columns of a state follow from the electron columns of its complex conjugate,
+μ_n[q][a][b] = (-1)ⁿ·conj μ_n[p][a⊕2][b⊕2] with w_p = conj(w_q), so two columns are run when every state's conjugate is
+among the states.
 """
 
 from __future__ import annotations
@@ -243,3 +250,138 @@ def green_map(system, energies, sites=None, *, broadening=None, moments: int | N
     info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
             "perf": perf[0] if len(perf) == 1 else perf}
     return GreenMap(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, sites, info)
+
+
+class GreenStates:
+    """Blocks of G(ε + iΓ) between the Nambu vectors of extended states.
+
+    `blocks` (Q, K, 4, 4) complex128: blocks[q, k][a, b] = <w_q a|G(E_k + iΓ_k)|w_q b> with |w b> = Σ_j w[j] e_{4j+b};
+    `energies` and `broadening` (K,), `states` the (Q, N) amplitudes, `momenta` the (Q, 3) wave vectors when the states
+    are the plane waves of `spectral_function` (else None), `info` the route details as in `GreenFunction`.  The
+    helpers are those of `GreenMap` with a state axis where it has a site axis.
+    """
+
+    def __init__(self, blocks: np.ndarray, energies: np.ndarray, broadening: np.ndarray, states: np.ndarray,
+                 info: dict | None = None, momenta: np.ndarray | None = None):
+        self.blocks = blocks
+        self.energies = energies
+        self.broadening = broadening
+        self.states = states
+        self.momenta = momenta
+        self.info = dict(info or {})
+
+    def spectral(self) -> np.ndarray:
+        """(Q, K) spin-summed electron spectral function -Im(G[0,0] + G[1,1])/π: A(k, ε) for plane waves."""
+        g = self.blocks
+        return -(g[:, :, 0, 0] + g[:, :, 1, 1]).imag / np.pi
+
+    def spin_spectral(self) -> np.ndarray:
+        """(Q, K, 2) -Im G[0,0]/π and -Im G[1,1]/π."""
+        g = self.blocks
+        return np.stack([-g[:, :, 0, 0].imag, -g[:, :, 1, 1].imag], axis=2) / np.pi
+
+    def spin_density(self) -> np.ndarray:
+        """(Q, K, 3) -Im tr(σ_k G[0:2, 0:2])/π for k = x, y, z."""
+        from .common import σ1, σ2, σ3
+
+        g = self.blocks[:, :, 0:2, 0:2]
+        return np.stack([-np.einsum("ab,qkba->qk", s, g).imag for s in (σ1, σ2, σ3)], axis=2) / np.pi
+
+    def anomalous(self) -> np.ndarray:
+        """(Q, K, 2, 2) the electron-hole blocks G[0:2, 2:4]: F(k, ε) for plane waves."""
+        return self.blocks[:, :, 0:2, 2:4].copy()
+
+
+def _conjugate_partners(states: np.ndarray):
+    """partner[q] = a row equal (`np.array_equal`) to conj(states[q]), or None if some state has no such row."""
+    def key(row):
+        return (row.view(np.float64) + 0.0).tobytes()  # (+ 0.0: -0.0 and 0.0 compare equal, so they share a key)
+
+    where = {}
+    for q, row in enumerate(states):
+        where.setdefault(key(row), q)
+    partner = np.empty(states.shape[0], dtype=np.int64)
+    for q, row in enumerate(states):
+        p = where.get(key(np.conj(row)))
+        if p is None:
+            return None
+        partner[q] = p
+    return partner
+
+
+def hole_columns_of_states(mu: np.ndarray, partner: np.ndarray) -> np.ndarray:
+    """(M, Q, 4, 4) moments from the electron columns (M, Q, 4, 2) of states whose conjugates are among them:
+    μ_n[q][a][b] = (-1)ⁿ conj μ_n[p][a⊕2][b⊕2] with w_p = conj(w_q), p = partner[q]."""
+    full = np.empty(mu.shape[:3] + (4,), dtype=np.complex128)
+    full[..., 0:2] = mu
+    sign = np.where(np.arange(mu.shape[0]) & 1, -1.0, 1.0)[:, None, None, None]
+    full[..., 2:4] = sign * mu[:, partner][:, :, [2, 3, 0, 1], :].conj()
+    return full
+
+
+def green_states(system, states, energies, *, broadening=None, moments: int | None = None, digits: float = 12.0,
+                 scale: float | None = None, _all_columns: bool = False, _momenta=None) -> GreenStates:
+    """<w a|G(E + iΓ)|w b> for the states `states` (see `Hamiltonian.green_states`)."""
+    states = np.array(states, dtype=np.complex128)
+    if states.ndim == 1:
+        states = states[None, :]
+    n_sites = system.lattice.size
+    if states.ndim != 2 or states.shape[0] < 1:
+        raise ValueError("green_states: states is empty (expected (Q, N) or (N,) amplitudes)")
+    if states.shape[1] != n_sites:
+        raise ValueError(f"green_states: states of {states.shape[1]} amplitudes for a lattice of {n_sites} sites")
+    if not np.all(np.isfinite(states)):
+        raise ValueError("green_states: the amplitudes must be finite")
+    energies, gamma, moments, scale = _series_arguments(system, energies, broadening, moments, digits, scale)
+
+    # particle-hole symmetry gives the hole columns of a state from the electron columns of its complex conjugate
+    partner = None
+    if not _all_columns and system.has_symmetric_spectrum(1e-12):
+        partner = _conjugate_partners(states)
+    derive = partner is not None
+    columns = 2 if derive else 4
+
+    # groups of states whose moment table stays under the host limit; a state and its partner share a group
+    per_state = moments * 4 * columns * 16
+    limit = max(1, HOST_TABLE_LIMIT // per_state)
+    groups, current, placed = [], [], np.zeros(states.shape[0], dtype=bool)
+    for q in range(states.shape[0]):
+        if placed[q]:
+            continue
+        unit = [q] if not derive or partner[q] == q else [q, int(partner[q])]
+        if current and len(current) + len(unit) > limit:
+            groups.append(current)
+            current = []
+        current.extend(unit)
+        placed[unit] = True
+    groups.append(current)
+
+    solver = system._solver()
+    z = energies + 1j * gamma
+    blocks = np.empty((states.shape[0], energies.size, 4, 4), dtype=np.complex128)
+    perf = []
+    for rows in groups:
+        rows = np.asarray(rows, dtype=np.int64)
+        distinct = np.unique(rows)
+        mu = solver.green_state_moments(scale, moments, states[distinct], columns)
+        perf.append(solver.perf())
+        if derive:  # (partners within the group: a repeated row may have met its partner in an earlier group too)
+            mu = hole_columns_of_states(mu, _conjugate_partners(states[distinct]))
+        blocks[distinct] = blocks_from_moments(mu, scale, z)
+    info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+            "perf": perf[0] if len(perf) == 1 else perf}
+    return GreenStates(blocks, energies, gamma, states, info, _momenta)
+
+
+def spectral_function(system, momenta, energies, **options) -> GreenStates:
+    """G(k, E + iΓ) in plane waves (see `Hamiltonian.spectral_function`)."""
+    momenta = np.asarray(momenta, dtype=float)
+    if momenta.size == 0:
+        raise ValueError("green_states: momenta is empty")
+    if momenta.ndim == 1:
+        momenta = momenta[None, :]
+    if momenta.ndim != 2 or momenta.shape[1] != 3:
+        raise ValueError(f"green_states: expected momenta of shape (Q, 3) or (3,), not {momenta.shape}")
+    if not np.all(np.isfinite(momenta)):
+        raise ValueError("green_states: the momenta must be finite")
+    return green_states(system, system.lattice.plane_waves(momenta), energies, _momenta=momenta, **options)

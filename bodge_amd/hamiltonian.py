@@ -519,6 +519,26 @@ class Hamiltonian:
 
         return green_map(self, energies, sites, **options)
 
+    def green_states(self, states, energies, **options):
+        """Blocks <w a|G(ε + iΓ)|w b> of the retarded Green's function between the four Nambu vectors of extended
+        states: `states` (Q, N) or (N,) holds one complex amplitude per site in site-index order (plane waves, wave
+        packets, standing waves, orbitals; it need not be normalised), and |w b> = Σ_j w[j] e_{4j+b}.  Returns a
+        `GreenStates` with the slices spectral(), spin_spectral(), spin_density(), anomalous().  Not part of the
+        reference API; options (broadening, moments, digits, scale) are those of `green`."""
+        from .green import green_states
+
+        return green_states(self, states, energies, **options)
+
+    def spectral_function(self, momenta, energies, **options):
+        """The momentum-resolved Green's function G(k, ε + iΓ) in the Nambu spinor (c_k↑, c_k↓, c†_-k↑, c†_-k↓):
+        `green_states` of the plane waves `lattice.plane_waves(momenta)`, `momenta` (Q, 3) or (3,) in radians per
+        lattice constant.  `spectral()` of the result is A(k, ε), `anomalous()` is F(k, ε); the momenta are kept on
+        the result.  On a disordered or textured system this is the unfolded band structure.  Not part of the
+        reference API; options as for `green_states`."""
+        from .green import spectral_function
+
+        return spectral_function(self, momenta, energies, **options)
+
     def apply(self, function, vectors, **options):
         """f(H) X for caller-supplied state vectors: `function` is a vectorised callable on real energies (it may be
         complex-valued), or None with `coefficients=` giving the Chebyshev series on [-scale, scale] directly.

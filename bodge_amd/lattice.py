@@ -95,6 +95,21 @@ class CubicLattice(Lattice):
         grid = np.indices((Lx, Ly, Lz), dtype=np.int64)
         return grid.reshape(3, -1).T.copy()
 
+    def plane_waves(self, momenta) -> np.ndarray:
+        """(Q, N) complex amplitudes exp(i k·r_j)/√N for the momenta `momenta` ((Q, 3), or (3,) for one: radians per
+        lattice constant), r_j from `site_array()`.  The phase is formed from k·r itself, so the waves of -k are the
+        complex conjugates of those of k bit for bit."""
+        k = np.asarray(momenta, dtype=float)
+        if k.ndim == 1:
+            k = k[None, :]
+        if k.ndim != 2 or k.shape[1] != 3:
+            raise ValueError(f"plane_waves: expected momenta of shape (Q, 3) or (3,), not {np.shape(momenta)}")
+        r = self.site_array().astype(float)
+        # (element by element, not a matrix product: a library's blocking may round k·r of one momentum differently
+        # from the same momentum in a batch, or from its negative)
+        phase = k[:, 0:1] * r[None, :, 0] + k[:, 1:2] * r[None, :, 1] + k[:, 2:3] * r[None, :, 2]
+        return np.exp(1j * phase) / np.sqrt(self.size)
+
     def _pair_table(self, axis: int, wrap: bool) -> np.ndarray:
         """(P, 2, 3) coordinates of unordered partner pairs along `axis`.
 

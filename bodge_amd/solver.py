@@ -302,6 +302,22 @@ class DeviceSolver:
             int(n_components), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def green_state_moments(self, scale, n_moments, amplitudes, n_components: int = 4) -> np.ndarray:
+        """(n_moments, n_states, 4, n_components) complex moments <w_q a|T_n(H/scale)|w_q b> of the states
+        `amplitudes` (n_states, n_sites): one complex amplitude per site, the same on every Nambu component
+        (bdg_green_state_moments)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        amplitudes = np.ascontiguousarray(amplitudes, dtype=np.complex128)
+        if amplitudes.ndim != 2 or amplitudes.shape[0] < 1 or amplitudes.shape[1] != self.n_sites:
+            raise ValueError(f"green_state_moments: expected amplitudes of shape (states, {self.n_sites})")
+        if int(n_moments) < 1 or int(n_components) not in (2, 4):
+            raise ValueError("green_state_moments: expected at least one moment and 2 or 4 components")
+        out = np.empty((int(n_moments), amplitudes.shape[0], 4, int(n_components)), dtype=np.complex128)
+        backend.check(self._lib.bdg_green_state_moments(
+            self._handle, float(scale), int(n_moments), amplitudes.shape[0], backend.as_f64p(amplitudes.view(np.float64)),
+            int(n_components), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def lanczos_begin(self, n_vectors: int, seed: int = 0, first_id: int = 0, kind: int = VEC_RADEMACHER,
                       max_iter: int = 10000) -> None:
         """Start n_vectors independent Lanczos processes on H^2 (see `lanczos_advance`)."""

@@ -91,13 +91,15 @@ typedef struct bdg_perf {
                               2 = the dictionary kernel (cheb_clenshaw_dict); 0 = the call was another one */
     int32_t green;         /* bdg_green_moments: 1 = its picked steps ran the streamed-block kernel (cheb_green),
                               2 = the dictionary kernel (cheb_green_dict); 0 = the call was another one */
-    int32_t green_ranges;  /* bdg_green_moments, bdg_green_local_moments: ranges of moments the device table was
-                              filled and copied out in */
+    int32_t green_ranges;  /* bdg_green_moments, bdg_green_local_moments, bdg_green_state_moments: ranges of moments the
+                              device table was filled and copied out in */
     int32_t green_local;   /* bdg_green_local_moments: 1 = its steps ran the streamed-block kernel (cheb_green_local),
                               2 = the dictionary kernel (cheb_green_local_dict); 0 = the call was another one */
     int32_t apply;         /* bdg_apply_series: 1 = its stored-source Clenshaw steps ran the streamed-block kernel
                               (cheb_clenshaw_vec), 2 = the dictionary kernel (cheb_clenshaw_vec_dict); 0 = the call was
                               another one */
+    int32_t green_states;  /* bdg_green_state_moments: 1 = its steps ran the streamed-block kernel (cheb_green_state),
+                              2 = the dictionary kernel (cheb_green_state_dict); 0 = the call was another one */
     int32_t correlation;   /* bdg_moment_matrix: 1 = the call was this one, 0 = another one */
     double gram_ms;        /* bdg_moment_matrix: HIP-event time of its Gram + reduce launches (corr_gram, corr_reduce) */
     double gram_flops;     /* bdg_moment_matrix: 8 x rows of X x rows of Y x K summed over the Gram launches, K = 4 nb x
@@ -280,6 +282,23 @@ int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t 
  */
 int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
                             const int32_t* block_rows, int32_t n_components, double* out);
+
+/*
+ * Chebyshev moments of the resolvent between extended states, for G(eps) in plane waves, wave packets or orbitals
+ * (DESIGN.md §16).  A state q is one complex amplitude per site, amplitudes[(q*nb + j)*2 + {0, 1}] = (re, im) of
+ * w_q[j] in site-index order; its Nambu vectors are |w_q b> = sum_j w_q[j] e_{4j + b}.
+ *   out[((((n*n_states + q)*4 + a)*n_components + b)*2 + {0, 1}] = (re, im) of <w_q a|T_n(H/scale)|w_q b>
+ * for n < n_moments, a < 4, b < n_components (2: the electron columns, 4: all).  A lane payload is one complex
+ * column in every arithmetic mode (as for bdg_apply_series): a batch holds the columns of up to 64 / n_components
+ * states (32 / n_components in real arithmetic) by the one-step width rule (bdg_set_lanes_per_row fixes the lanes).
+ * One launch per moment advances all of them and projects t_{n+1} on the states (kernels cheb_green_state /
+ * cheb_green_state_dict: one partial per workgroup, no atomics); green_state_reduce sums the partials of a range of
+ * moments in a fixed order.  Partials and table of a range take at most 256 MB (BODGE_AMD_GREEN_TABLE_BYTES); the
+ * table is copied into `out` when the range is full.  bdg_perf_query reports the call (`green_states` says which
+ * kernel form ran).  Whole matrices only (not slabs).
+ */
+int bdg_green_state_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_states,
+                            const double* amplitudes, int32_t n_components, double* out);
 
 /* Per-start-vector moments for unit vectors: mu_out[m*n_vectors + r]. */
 int bdg_cheb_diag_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_vectors,
