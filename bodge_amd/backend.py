@@ -115,6 +115,14 @@ SIGNATURES = {
     "bdg_lanczos_ritz_vectors": (C.c_int, [_handle, C.c_int32, C.c_int32, _f64p, _f64p]),
     "bdg_lanczos_ritz_pairs": (C.c_int, [_handle, C.c_int32, C.c_int32, _f64p, _f64p, C.c_double, C.c_int32,
                                         C.POINTER(C.c_int32), _f64p, _f64p]),
+    "bdg_subspace_begin": (C.c_int, [_handle, C.c_int32, C.c_uint64, C.c_uint64]),
+    "bdg_subspace_end": (C.c_int, [_handle]),
+    "bdg_subspace_filter": (C.c_int, [_handle, C.c_double, C.c_int32, _f64p]),
+    "bdg_subspace_project": (C.c_int, [_handle, _f64p, _f64p]),
+    "bdg_subspace_rotate": (C.c_int, [_handle, C.c_int32, _f64p, _f64p, _f64p]),
+    "bdg_subspace_refill": (C.c_int, [_handle, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64]),
+    "bdg_subspace_read": (C.c_int, [_handle, C.c_int32, C.c_int32, _f64p]),
+    "bdg_subspace_write": (C.c_int, [_handle, C.c_int32, C.c_int32, _f64p]),
     "bdg_random_vector": (C.c_int, [_handle, C.c_uint64, C.c_uint64, C.c_int32, _f64p]),
     "bdg_eigh_dense": (C.c_int, [_handle, _f64p, _f64p]),
     "bdg_eigh_dense_above": (C.c_int, [_handle, C.c_double, C.c_int64, _f64p, C.POINTER(C.c_int64), _f64p]),

@@ -413,22 +413,18 @@ double apply_bytes(const bdg_system* sys, int vectors, const ModeInfo& mode, boo
            mode.entry_bytes / 3.0 * (double)vectors * (double)sys->nb + 16.0 * n_functions;
 }
 
-int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functions, const double* coef, int n_vectors,
-                     const double* x, double* y_out) {
-    // (argument errors first, the scalar ones before the handle is looked at: none of them needs a GPU)
-    if (n_moments < 1) return fail(BDG_EINVAL, "n_moments must be >= 1");
-    if (n_functions < 1) return fail(BDG_EINVAL, "n_functions must be >= 1");
-    if (n_vectors < 1) return fail(BDG_EINVAL, "n_vectors must be >= 1");
-    if (!(scale > 0.0)) return fail(BDG_EINVAL, "scale must be positive");
-    if (!coef || !x || !y_out) return fail(BDG_EINVAL, "null argument");
-    if (!sys) return fail(BDG_EINVAL, "null system handle");
-    if (sys->ncols != sys->nb || sys->row_offset != 0)
-        return fail(BDG_EINVAL, "bdg_apply_series needs a whole (square) matrix: slabs are not supported");
+// The batch loop of a stored-source series: the columns (vector, function) of the call in batches of the one-step
+// width, every batch staged site-major in vec_d on the way in and on the way out.  `x` and `y_out` are host arrays
+// (bdg_apply_series) or, with `on_device`, device arrays in the same vector-major order (the block of subspace.hpp:
+// the staging buffer is then filled from and emptied to the block; x == y_out is allowed when n_functions == 1, a
+// batch reads and writes its own columns only).  `coef` is on the host in both cases.  `record` = leave the call's
+// figures in sys->perf.
+int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_functions, const double* coef, int n_vectors,
+                         const double* x, double* y_out, bool on_device, bool record) {
     const int64_t n_columns = (int64_t)n_vectors * n_functions;
-    if (n_columns > INT32_MAX) return fail(BDG_EINVAL, "n_vectors x n_functions exceeds 2^31 - 1 columns");
     const int64_t nb = sys->nb;
-    lanczos_free(sys);
-    HIP_TRY(hipSetDevice(sys->device));
+    const hipMemcpyKind kind_in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind kind_out = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 
     // Real arithmetic whenever the matrix is real: the columns may be complex all the same (Re and Im in the two
     // slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
@@ -517,7 +513,7 @@ int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functio
                 const int v_lo = ca.col_base / n_functions;
                 const int v_hi = (ca.col_base + ca.n_active - 1) / n_functions;
                 HIP_TRY(hipMemcpyAsync(set->vec_d.ptr, x + (size_t)2 * vec_len * v_lo,
-                                       sizeof(double2) * vec_len * (size_t)(v_hi - v_lo + 1), hipMemcpyHostToDevice, set->stream));
+                                       sizeof(double2) * vec_len * (size_t)(v_hi - v_lo + 1), kind_in, set->stream));
                 bdg::apply_scatter<<<fill_grid, 256, 0, set->stream>>>(set->vec_d.ptr, set->vec_c.ptr, nb, rl, ca.n_active,
                                                                         ca.col_base, n_functions, v_lo);
                 bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_a.ptr, (int64_t)vec_count);
@@ -551,7 +547,7 @@ int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functio
             for (int b = first; b < last; ++b) {
                 const size_t q = (size_t)(b - first);
                 HIP_TRY(hipMemcpyAsync(y_out + (size_t)2 * vec_len * args[q].col_base, sets[q]->vec_d.ptr,
-                                       sizeof(double2) * vec_len * (size_t)args[q].n_active, hipMemcpyDeviceToHost, sets[q]->stream));
+                                       sizeof(double2) * vec_len * (size_t)args[q].n_active, kind_out, sets[q]->stream));
             }
         }
         for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamSynchronize(sets[(size_t)s]->stream));
@@ -582,7 +578,7 @@ int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functio
         perf.streams = n_streams;
         perf.groups_per_launch = 1;
         perf.apply = plan.dictionary ? 2 : 1;
-        sys->perf = perf;
+        if (record) sys->perf = perf;
         return BDG_OK;
     };
     const int rc = body();
@@ -594,6 +590,23 @@ int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functio
         if (ev) (void)hipEventDestroy(ev);
     d_coef.release();
     return rc;
+}
+
+int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functions, const double* coef, int n_vectors,
+                     const double* x, double* y_out) {
+    // (argument errors first, the scalar ones before the handle is looked at: none of them needs a GPU)
+    if (n_moments < 1) return fail(BDG_EINVAL, "n_moments must be >= 1");
+    if (n_functions < 1) return fail(BDG_EINVAL, "n_functions must be >= 1");
+    if (n_vectors < 1) return fail(BDG_EINVAL, "n_vectors must be >= 1");
+    if (!(scale > 0.0)) return fail(BDG_EINVAL, "scale must be positive");
+    if (!coef || !x || !y_out) return fail(BDG_EINVAL, "null argument");
+    if (!sys) return fail(BDG_EINVAL, "null system handle");
+    if (sys->ncols != sys->nb || sys->row_offset != 0)
+        return fail(BDG_EINVAL, "bdg_apply_series needs a whole (square) matrix: slabs are not supported");
+    if ((int64_t)n_vectors * n_functions > INT32_MAX) return fail(BDG_EINVAL, "n_vectors x n_functions exceeds 2^31 - 1 columns");
+    lanczos_free(sys);
+    HIP_TRY(hipSetDevice(sys->device));
+    return apply_series_batches(sys, scale, n_moments, n_functions, coef, n_vectors, x, y_out, false, true);
 }
 
 }  // namespace

@@ -13,6 +13,7 @@
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
+//   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver
 //   tridiag.hpp     eigenvalues only: Householder tridiagonalisation + bisection (no library)
 // and the kernels in kernels.hpp / sweep.hpp, the CPU-thread helpers in host_assembly.hpp.
@@ -65,6 +66,7 @@
 #include "green_map.hpp"
 #include "green_states.hpp"
 #include "lanczos.hpp"
+#include "subspace.hpp"
 #include "dense.hpp"
 #include "tridiag.hpp"
 
@@ -529,6 +531,7 @@ int bdg_destroy(bdg_system* sys) {
     sys->side_sets.clear();
     if (sys->ev_side) (void)hipEventDestroy(sys->ev_side);
     lanczos_free(sys);
+    subspace_free(sys);
     sys->indptr.release();
     sys->indices.release();
     sys->blocks.release();
@@ -755,6 +758,7 @@ int bdg_eigh_dense(bdg_system* sys, double* w_out, double* z_out) {
     if (!sys || !w_out) return fail(BDG_EINVAL, "null argument");
     if (sys->ncols != sys->nb) return fail(BDG_EINVAL, "bdg_eigh_dense needs a whole (square) matrix, not a slab");
     lanczos_free(sys);
+    subspace_free(sys);
     HIP_TRY(hipSetDevice(sys->device));
     release_side_sets(sys);  // (the dense arrays want the memory)
     const int64_t n = 4 * sys->nb;
@@ -916,6 +920,7 @@ int bdg_eigh_dense_above(bdg_system* sys, double lower_bound, int64_t capacity, 
     const bool own = forced ? std::string(forced) == "tridiagonal" : n > 512;
     if (own) {
         lanczos_free(sys);
+        subspace_free(sys);
         HIP_TRY(hipSetDevice(sys->device));
         release_side_sets(sys);
         return eig_tridiagonal_above(sys, w_out, lower_bound, capacity, n_vectors, z_out);
@@ -1033,6 +1038,7 @@ int bdg_lanczos_begin(bdg_system* sys, int32_t n_vectors, uint64_t seed, uint64_
     start.vec_kind = vec_kind;
     (void)hipSetDevice(sys->device);
     release_side_sets(sys);  // (a Lanczos run keeps up to k + 4 vector buffers of its own)
+    subspace_free(sys);
     return lanczos_begin(sys, n_vectors, start, max_iter);
 }
 
@@ -1051,6 +1057,39 @@ int bdg_lanczos_ritz_pairs(bdg_system* sys, int32_t n_iter, int32_t n_levels, co
     if (!sys || !coef || !eps) return fail(BDG_EINVAL, "null argument");
     if (!(rank_tol >= 0.0 && rank_tol < 1.0)) return fail(BDG_EINVAL, "rank_tol must lie in [0, 1)");
     return lanczos_ritz_pairs(sys, n_iter, n_levels, coef, eps, rank_tol, max_out, n_out, values_out, vectors_out);
+}
+
+int bdg_subspace_begin(bdg_system* sys, int32_t n_columns, uint64_t seed, uint64_t first_vec_id) {
+    return subspace_begin(sys, n_columns, seed, first_vec_id);
+}
+
+int bdg_subspace_end(bdg_system* sys) {
+    if (!sys) return fail(BDG_EINVAL, "null system handle");
+    (void)hipSetDevice(sys->device);
+    subspace_free(sys);
+    return BDG_OK;
+}
+
+int bdg_subspace_filter(bdg_system* sys, double scale, int32_t n_moments, const double* coef) {
+    return subspace_filter(sys, scale, n_moments, coef);
+}
+
+int bdg_subspace_project(bdg_system* sys, double* s_out, double* g_out) { return subspace_project(sys, s_out, g_out); }
+
+int bdg_subspace_rotate(bdg_system* sys, int32_t n_out, const double* q, const double* theta, double* residual_out) {
+    return subspace_rotate_block(sys, n_out, q, theta, residual_out);
+}
+
+int bdg_subspace_refill(bdg_system* sys, int32_t first_column, int32_t count, uint64_t seed, uint64_t first_vec_id) {
+    return subspace_refill(sys, first_column, count, seed, first_vec_id);
+}
+
+int bdg_subspace_read(bdg_system* sys, int32_t first_column, int32_t count, double* out) {
+    return subspace_copy(sys, first_column, count, nullptr, out);
+}
+
+int bdg_subspace_write(bdg_system* sys, int32_t first_column, int32_t count, const double* x) {
+    return subspace_copy(sys, first_column, count, x, nullptr);
 }
 
 int bdg_perf_query(bdg_system* sys, bdg_perf* out) {

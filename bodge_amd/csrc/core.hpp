@@ -62,6 +62,9 @@ namespace {
 // A Lanczos run keeps pointers into the handle's vector buffers; any other call that refills or
 // reallocates them ends the run first (bdg_lanczos_advance then reports that begin is needed).
 void lanczos_free(bdg_system* sys);
+// A subspace block (subspace.hpp) keeps three arrays of its own on the device; a dense solve or a Lanczos run,
+// which want the memory, end it (the later bdg_subspace_* calls then report that begin is needed).
+void subspace_free(bdg_system* sys);
 }
 
 struct ExchangePeer {
@@ -174,6 +177,7 @@ struct bdg_system : StreamSet {
     DeviceBuffer<int> tiles_interior, tiles_boundary;
     int split_rows_per_tile = 0, n_interior = 0, n_boundary = 0;
     void* lanczos = nullptr;  // LanczosState of a run in progress (defined with the driver)
+    void* subspace = nullptr;  // SubspaceState of a device-resident block (subspace.hpp)
     int max_row_blocks = 0;
     int64_t bandwidth = 0;  // max |column - row| over the stored blocks (square matrices)
     int num_cus = 0;

@@ -491,6 +491,16 @@ class Hamiltonian:
 
         return lowest_eigenpairs(self, k, **options)
 
+    def eigenpairs(self, window, **options):
+        """Every eigenpair with lo <= E <= hi for window = (lo, hi), ascending, with orthonormal eigenvectors
+        (layouts of `diagonalize`), by Chebyshev-filtered subspace iteration on a block of vectors that stays on
+        the GPU: the window may lie anywhere in the band and the number of states in it need not be known.  Its
+        edges belong in spectral gaps wider than about πa/moments.  Not part of the reference API; options
+        (moments, tol, max_iter, max_states, seed, format, method) are those of `bodge_amd.eigenpairs.eigenpairs`."""
+        from .eigenpairs import eigenpairs
+
+        return eigenpairs(self, window, **options)
+
     def fermi_matrix(self, temperature: float, **options):
         """Local one-body density matrix: the blocks of f(H), f(ε) = 1/(1 + e^{ε/T}), on the block skeleton
         of this Hamiltonian (every site and bond, zero blocks included), as a `FermiMatrix` with the

@@ -367,6 +367,82 @@ class DeviceSolver:
         kept = min(k, found.value)
         return values[:kept], vectors[:kept], found.value
 
+    # ------------------------------------------------------------------ subspace block
+    def subspace_begin(self, n_columns: int, seed: int = 0, first_id: int = 0) -> None:
+        """Allocate a device-resident block of `n_columns` vectors (X, HX and a rotation target) and fill X with the
+        Rademacher start vectors (seed, first_id + c) (bdg_subspace_begin).  A dense solve or a Lanczos run on the
+        handle ends the block."""
+        self._lanczos_vectors = 0  # (the library ends a Lanczos run: the block wants the memory)
+        self._subspace_columns = 0
+        backend.check(self._lib.bdg_subspace_begin(self._handle, int(n_columns), int(seed), int(first_id)))
+        self._subspace_columns = int(n_columns)
+
+    def subspace_end(self) -> None:
+        self._subspace_columns = 0
+        backend.check(self._lib.bdg_subspace_end(self._handle))
+
+    def _subspace_width(self, name: str) -> int:
+        # (`_subspace_columns` sizes the outputs.  A dense solve or a Lanczos run ends the block inside the library
+        # and does not reset it here: the library's own refusal, with its message, is what the caller then gets)
+        width = getattr(self, "_subspace_columns", 0)
+        if not width:
+            raise ValueError(f"bodge_hip: {name}: subspace_begin has not been called on this handle")
+        return width
+
+    def subspace_filter(self, scale, coef) -> None:
+        """X <- Σ_k coef[k] T_k(H/scale) X for real coefficients (bdg_subspace_filter)."""
+        self._subspace_width("subspace_filter")
+        self._lanczos_vectors = 0
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 1 or coef.size < 1:
+            raise ValueError("subspace_filter: expected real coefficients of shape (moments,)")
+        backend.check(self._lib.bdg_subspace_filter(self._handle, float(scale), coef.size, backend.as_f64p(coef)))
+
+    def subspace_project(self):
+        """HX <- H X; returns (S, G) = (X†X, X†HX), each (B, B) complex (bdg_subspace_project)."""
+        width = self._subspace_width("subspace_project")
+        self._lanczos_vectors = 0
+        s = np.empty((width, width), dtype=np.complex128)
+        g = np.empty((width, width), dtype=np.complex128)
+        backend.check(self._lib.bdg_subspace_project(self._handle, backend.as_f64p(s.view(np.float64)),
+                                                     backend.as_f64p(g.view(np.float64))))
+        return s, g
+
+    def subspace_rotate(self, q, theta) -> np.ndarray:
+        """X <- X Q, HX <- HX Q for Q (B, r) complex; returns the r residual norms ‖HX_j − θ_j X_j‖
+        (bdg_subspace_rotate).  Columns from r on are dead afterwards."""
+        width = self._subspace_width("subspace_rotate")
+        q = np.ascontiguousarray(q, dtype=np.complex128)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        if q.ndim != 2 or q.shape[0] != width or not 1 <= q.shape[1] <= width or theta.shape != (q.shape[1],):
+            raise ValueError(f"subspace_rotate: expected Q of shape ({width}, r <= {width}) and theta of shape (r,)")
+        residual = np.empty(q.shape[1])
+        backend.check(self._lib.bdg_subspace_rotate(self._handle, q.shape[1], backend.as_f64p(q.view(np.float64)),
+                                                    backend.as_f64p(theta), backend.as_f64p(residual)))
+        return residual
+
+    def subspace_refill(self, first_column: int, count: int, seed: int = 0, first_id: int = 0) -> None:
+        """X[first_column + c] <- start vector (seed, first_id + c) for c < count (bdg_subspace_refill)."""
+        self._subspace_width("subspace_refill")
+        backend.check(self._lib.bdg_subspace_refill(self._handle, int(first_column), int(count), int(seed), int(first_id)))
+
+    def subspace_read(self, first_column: int, count: int) -> np.ndarray:
+        """(count, 4N) complex: the columns of X from `first_column` on, one per row (bdg_subspace_read)."""
+        width = self._subspace_width("subspace_read")
+        if first_column < 0 or count < 1 or first_column + count > width:
+            raise ValueError(f"subspace_read: columns [{first_column}, {first_column + count}) are not within the block's {width}")
+        out = np.empty((int(count), self.dim), dtype=np.complex128)
+        backend.check(self._lib.bdg_subspace_read(self._handle, int(first_column), int(count), backend.as_f64p(out.view(np.float64))))
+        return out
+
+    def subspace_write(self, first_column: int, x) -> None:
+        """X[first_column + c] <- x[c] for the rows of x (count, 4N) (bdg_subspace_write)."""
+        width = self._subspace_width("subspace_write")
+        x = np.ascontiguousarray(x, dtype=np.complex128)
+        if x.ndim != 2 or x.shape[0] < 1 or x.shape[1] != self.dim or first_column < 0 or first_column + x.shape[0] > width:
+            raise ValueError(f"subspace_write: expected (count, {self.dim}) vectors within the block's {width} columns")
+        backend.check(self._lib.bdg_subspace_write(self._handle, int(first_column), x.shape[0], backend.as_f64p(x.view(np.float64))))
+
     def eigh(self, vectors: bool = True):
         """All eigenvalues ascending (and ALL eigenvectors as columns).  Eigenvalues alone: the library's own kernels
         at every size (Jacobi up to 4N = 512, tridiagonalisation + bisection above, through a band from 5000 rows for

@@ -342,6 +342,41 @@ int bdg_lanczos_ritz_pairs(bdg_system* sys, int32_t n_iter, int32_t n_levels, co
                            const double* eps, double rank_tol, int32_t max_out, int32_t* n_out,
                            double* values_out, double* vectors_out);
 
+/*
+ * A block of vectors that stays on the device (filtered subspace iteration).  The block is two arrays
+ * X and HX of n_columns columns, vector-major: column c is 4*nb contiguous complex entries in the order of bdg_spmv.
+ * A third array of the same size takes the out-of-place rotations.  The block hangs off the handle; a dense solve
+ * (bdg_eigh_dense, bdg_eigh_dense_above) or bdg_lanczos_begin on the handle ends it (they need the memory), and
+ * every later bdg_subspace_* call but `begin` and `end` then returns BDG_EINVAL with a message, as it does when
+ * `begin` was never called.  A failed allocation is reported (BDG_ENOMEM) and not retried: the handle is left
+ * without a block.  Whole matrices only: slabs return BDG_EINVAL.
+ *
+ *   begin    allocate for n_columns <= 4096 columns; X[c] = the Rademacher start vector (seed, first_vec_id + c) of
+ *            bdg_random_vector, HX = 0.  Replaces a block the handle already has.
+ *   end      free the block (no error if there is none).
+ *   filter   X <- sum_k coef[k] T_k(H/scale) X, k < n_moments, real coefficients, c_0 as it enters the sum: the
+ *            stored-source Clenshaw kernels and the batching of bdg_apply_series, a batch's staging buffer filled
+ *            from and emptied to the block instead of the host.  bdg_perf_query reports it like bdg_apply_series.
+ *   project  HX <- H X (one step of the same kernels), then s_out = X^† X and g_out = X^† HX, n_columns x n_columns
+ *            complex each, row-major (entry [n][m] = sum_k conj(X[n][k]) Y[m][k]): corr_gram on slices of 4096
+ *            entries, corr_reduce over the slices in ascending order, no atomics.
+ *   rotate   X <- X Q and HX <- HX Q for q = Q, n_columns x n_out complex, row-major (out[j][k] = sum_b Q[b][j]
+ *            X[b][k]; kernel subspace_rotate, fp64 MFMA), then residual_out[j] = |HX_j - theta[j] X_j|_2, j < n_out
+ *            (subspace_residual: one partial per workgroup and column; subspace_residual_reduce: their sum in
+ *            ascending order).  Columns >= n_out are dead afterwards (finite, but unspecified) until refilled.
+ *   refill   X[first_column + c] = start vector (seed, first_vec_id + c), c < count.  HX is not touched.
+ *   read     `count` columns of X from first_column on to out (count * 4*nb complex entries).
+ *   write    the same columns from x.
+ */
+int bdg_subspace_begin(bdg_system* sys, int32_t n_columns, uint64_t seed, uint64_t first_vec_id);
+int bdg_subspace_end(bdg_system* sys);
+int bdg_subspace_filter(bdg_system* sys, double scale, int32_t n_moments, const double* coef);
+int bdg_subspace_project(bdg_system* sys, double* s_out, double* g_out);
+int bdg_subspace_rotate(bdg_system* sys, int32_t n_out, const double* q, const double* theta, double* residual_out);
+int bdg_subspace_refill(bdg_system* sys, int32_t first_column, int32_t count, uint64_t seed, uint64_t first_vec_id);
+int bdg_subspace_read(bdg_system* sys, int32_t first_column, int32_t count, double* out);
+int bdg_subspace_write(bdg_system* sys, int32_t first_column, int32_t count, const double* x);
+
 /* Write the counter-based start vector (4*nb complex entries) to a host buffer. */
 int bdg_random_vector(bdg_system* sys, uint64_t seed, uint64_t vec_id, int32_t vec_kind,
                       double* v_out);
