@@ -46,275 +46,47 @@ __device__ inline void add_stored_source(double2& v, double2 c, double2 x) {
     v.y = fma(c.y, x.x, v.y);
 }
 
-// Generic form: cheb_clenshaw's tile loop (LDS staging of the streamed blocks, gathers of b_{k+1}) with the
-// epilogue b_k = coef * (H b_{k+1}) - b_{k+2} + c_k x.
-template <typename Mode, int RL>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw_vec(ApplyArgs ca) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ca.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int s = lane / RL;
-    const int r = lane % RL;
-    const int region = a.stage_blocks * STRIDE;
-    double2* stage = lds + wave * region;
-    const double2* all_blocks = static_cast<const double2*>(a.blocks);
-    const int fn = apply_function(ca, r);
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-
-    for (int t = t_lo + slot; t < t_hi; t += slots) {
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        const int row0 = (tile * kWavesPerBlock + wave) * RW;
-        if (row0 >= a.nb) continue;
-        const int row_end = min(row0 + RW, a.nb);
-        const int kb0 = a.indptr[row0];
-        const int kb1 = a.indptr[row_end];
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        int kbeg = 0, kend = 0;
-        if (valid) {
-            kbeg = a.indptr[i];
-            kend = a.indptr[i + 1];
-        }
-        double2 acc[4];
-#pragma unroll
-        for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-
-        for (int c0 = kb0; c0 < kb1; c0 += a.stage_blocks) {
-            const int c1 = min(c0 + a.stage_blocks, kb1);
-            const int n_el = (c1 - c0) * SPB;
-            const double2* src = all_blocks + (size_t)c0 * SPB;
-            for (int e0 = 0; e0 < n_el; e0 += 4 * kWave) {
-                double2 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) v[u] = load_stream(src + e);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) stage[(e / SPB) * STRIDE + (e % SPB)] = v[u];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-            const int k0 = max(kbeg, c0), k1 = min(kend, c1);
-            double2 x[4], xn[4];
-            if (k0 < k1) {
-                const size_t j = (size_t)a.indices[k0];
-#pragma unroll
-                for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-            }
-            for (int k = k0; k < k1; ++k) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                if (k + 1 < k1) {
-                    const size_t j = (size_t)a.indices[k + 1];
-#pragma unroll
-                    for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-                }
-                Mode::mac_row(acc, stage + (k - c0) * STRIDE, x);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
-
-        if (valid) {
+// The tail of the stored-source Clenshaw step b_k = coef * (H b_{k+1}) - b_{k+2} + c_k x on the shared tile loops
+// (family.hpp): the column's coefficient, and before the store one more vector load (x, into the tile loop's dead
+// registers) and the complex multiply-add.  The two forms carry the coefficient differently, each as its registers
+// allow: the dictionary form reads it once per kernel; the streamed-block form keeps only the function index.
+template <bool DICTIONARY>
+struct ApplyTail : FamilyTail {
+    using Args = ApplyArgs;
+    static constexpr const char* kFamily = "stored-source Clenshaw";
+    using Column = std::conditional_t<DICTIONARY, double2, int>;
+    template <typename Mode, int RL>
+    __device__ static Column begin(const ApplyArgs& ca, int r, double2*) {
+        if constexpr (DICTIONARY) return apply_coefficient(ca, apply_function(ca, r));
+        else return apply_function(ca, r);
+    }
+    template <typename Mode, int RL>
+    __device__ static double2 row(const ApplyArgs& ca, Column column, int) {
+        if constexpr (DICTIONARY) {
+            return column;
+        } else {
             // Read here and not before the tile loop, and from an index the compiler cannot see through: the kernel
             // is at its 128 registers across that loop, and a coefficient (or its address) kept there spills
             // (ComplexPHMode, 12 - 20 bytes per lane with hipcc of ROCm 7.2.0, AMD clang 22.0.0git: checked on that
             // compiler only - tests/test_apply_host.py pins scratch = 0 for every instance, so another compiler that
             // sees through the empty asm, or needs no such help, shows up there).
-            int f = fn;
+            int f = column;
             asm volatile("" : "+v"(f));
-            const double2 ck = apply_coefficient(ca, f);
-            double2 nx[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                const double2 p = (a.stream_vectors & 1) ? load_stream(a.prev + own) : a.prev[own];
-                nx[al].x = fma(a.coef, acc[al].x, -p.x);
-                nx[al].y = fma(a.coef, acc[al].y, -p.y);
-            }
-            // (the accumulators are free from here on: the source takes their place)
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                acc[al] = (a.stream_vectors & 1) ? load_stream(ca.x + own) : ca.x[own];
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                add_stored_source(nx[al], ck, acc[al]);
-                if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
-                else a.prev[own] = nx[al];
-            }
+            return apply_coefficient(ca, f);
         }
     }
-}
-
-// Dictionary form: cheb_clenshaw_dict's tile loop (block table in LDS, fixed-width row words, own and
-// neighbouring rows of b_{k+1} shared through LDS) with the stored-source epilogue.
-template <typename Mode, int RL, int MAXB>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw_vec_dict(ApplyArgs ca) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ca.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int s = lane / RL;
-    const int r = lane % RL;
-    const double2 ck = apply_coefficient(ca, apply_function(ca, r));
-
-    const double2* table = static_cast<const double2*>(a.dict_table);
-    for (int e = threadIdx.x; e < a.n_unique * SPB; e += kBlockThreads)
-        lds[(e / SPB) * STRIDE + (e % SPB)] = table[e];
-    double2* share = lds + a.n_unique * STRIDE + wave * (kWave * 4);
-    __syncthreads();
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-    auto first_row = [&](int t) {
-        if (t >= t_hi) return a.nb;
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        return (tile * kWavesPerBlock + wave) * RW;
-    };
-    struct RowMeta {
-        int len;
-        unsigned word[MAXB];
-    };
-    auto col_of = [](unsigned w) { return (size_t)(w & 0xFFFFFFu); };
-    auto id_of = [](unsigned w) { return (int)(w >> 24); };
-    constexpr int ELLW = MAXB <= 3 ? 4 : 8;
-    auto load_meta = [&](int row0, RowMeta& m) {
-        const int i = row0 + s;
-        const uint4* src = reinterpret_cast<const uint4*>(a.dict_ell) + (size_t)min(i, a.nb - 1) * (ELLW / 4);
-        unsigned words[8];
-        const uint4 lo = src[0];
-        words[0] = lo.x, words[1] = lo.y, words[2] = lo.z, words[3] = lo.w;
-        if constexpr (ELLW == 8) {
-            const uint4 hi = src[1];
-            words[4] = hi.x, words[5] = hi.y, words[6] = hi.z, words[7] = hi.w;
-        } else {
-            words[4] = words[5] = words[6] = words[7] = 0xFFFFFFFFu;
+    template <typename Mode, int RL>
+    __device__ static void amend(const ApplyArgs& ca, double2 ck, int i, int r, double2 nx[4], double2 x[4]) {
+        const StepArgs& a = ca.s;
+#pragma unroll
+        for (int al = 0; al < 4; ++al) {
+            const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
+            x[al] = (a.stream_vectors & 1) ? load_stream(ca.x + own) : ca.x[own];
         }
-        m.len = 0;
 #pragma unroll
-        for (int q = 0; q < MAXB; ++q) {
-            const bool there = i < a.nb && words[q] != 0xFFFFFFFFu;
-            m.len += there ? 1 : 0;
-            m.word[q] = there ? words[q] : 0u;
-        }
-    };
-
-    int pos = t_lo + slot;
-    int row0 = first_row(pos);
-    RowMeta meta;
-    load_meta(row0, meta);
-    for (; pos < t_hi; pos += slots) {
-        const int row0_n = first_row(pos + slots);
-        RowMeta meta_n;
-        load_meta(row0_n, meta_n);
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        {
-            double2 own[4];
-#pragma unroll
-            for (int be = 0; be < 4; ++be)
-                own[be] = valid ? a.cur[vslot(be, (size_t)i, r, a.ncols, RL)] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int be = 0; be < 4; ++be) share[SHARE_SLOT(lane, be)] = own[be];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-        if (valid) {
-            auto source = [&](unsigned w) {
-                const long d = (long)col_of(w) - (long)i;
-                const long ss = (long)s + d;
-                return (ss >= 0 && ss < RW && (long)i + d < a.nb) ? (int)d : (int)kWave;
-            };
-            double2 acc[4], x[4], xn[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-            if (meta.len > 0 && source(meta.word[0]) == kWave) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be)
-                    xn[be] = a.cur[vslot(be, col_of(meta.word[0]), r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int q = 0; q < MAXB; ++q) {
-                if (q < meta.len) {
-                    const int src = source(meta.word[q]);
-                    if (src == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                    } else {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = share[SHARE_SLOT(lane + src * RL, be)];
-                    }
-                    if (q + 1 < MAXB && q + 1 < meta.len && source(meta.word[q + 1 < MAXB ? q + 1 : 0]) == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be)
-                            xn[be] = a.cur[vslot(be, col_of(meta.word[q + 1 < MAXB ? q + 1 : 0]), r, a.ncols, RL)];
-                    }
-                    Mode::mac_row(acc, lds + id_of(meta.word[q]) * STRIDE, x);
-                }
-            }
-            // (x[] is free from here on: it takes the stored source)
-            double2 p[4];
-            if (a.stream_vectors & 1) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = load_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL));
-#pragma unroll
-                for (int al = 0; al < 4; ++al) x[al] = load_stream(ca.x + vslot(al, (size_t)i, r, a.ncols, RL));
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = a.prev[vslot(al, (size_t)i, r, a.ncols, RL)];
-#pragma unroll
-                for (int al = 0; al < 4; ++al) x[al] = ca.x[vslot(al, (size_t)i, r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                p[al].x = fma(a.coef, acc[al].x, -p[al].x);
-                p[al].y = fma(a.coef, acc[al].y, -p[al].y);
-                add_stored_source(p[al], ck, x[al]);
-            }
-            if (a.stream_vectors & 2) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) store_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL), p[al]);
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) a.prev[vslot(al, (size_t)i, r, a.ncols, RL)] = p[al];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        row0 = row0_n;
-        meta = meta_n;
+        for (int al = 0; al < 4; ++al) add_stored_source(nx[al], ck, x[al]);
     }
-}
+};
 
 // Host vectors (site-major complex, `n_stage` of them one after the other, the first being vector `vec_base`
 // of the call) into the batch layout: column r takes vector (col_base + r) / n_functions, padding columns 0.
@@ -347,64 +119,7 @@ __global__ void apply_gather(const double2* __restrict__ planar, double2* __rest
 
 namespace {
 
-using ApplyKernel = void (*)(bdg::ApplyArgs);
-
-template <typename Mode>
-ApplyKernel apply_generic_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_clenshaw_vec<Mode, 4>;
-        case 8: return bdg::cheb_clenshaw_vec<Mode, 8>;
-        case 16: return bdg::cheb_clenshaw_vec<Mode, 16>;
-        case 32: return bdg::cheb_clenshaw_vec<Mode, 32>;
-        case 64: return bdg::cheb_clenshaw_vec<Mode, 64>;
-    }
-    return nullptr;
-}
-
-template <typename Mode, int MAXB>
-ApplyKernel apply_dict_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_clenshaw_vec_dict<Mode, 4, MAXB>;
-        case 8: return bdg::cheb_clenshaw_vec_dict<Mode, 8, MAXB>;
-        case 16: return bdg::cheb_clenshaw_vec_dict<Mode, 16, MAXB>;
-        case 32: return bdg::cheb_clenshaw_vec_dict<Mode, 32, MAXB>;
-    }
-    // (64 lanes: complex modes only, as for the one-step dictionary kernel)
-    if constexpr (Mode::kVec == 1)
-        if (rl == 64) return bdg::cheb_clenshaw_vec_dict<Mode, 64, MAXB>;
-    return nullptr;
-}
-
-template <typename Mode>
-ApplyKernel apply_kernel_for(bool dictionary, int max_row_blocks, int rl) {
-    if (!dictionary) return apply_generic_for<Mode>(rl);
-    if (max_row_blocks <= 3) return apply_dict_for<Mode, 3>(rl);
-    if (max_row_blocks <= 5) return apply_dict_for<Mode, 5>(rl);
-    return apply_dict_for<Mode, 7>(rl);
-}
-
-ApplyKernel apply_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
-    switch (mode.id) {
-        case 1: return apply_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
-        case 2: return apply_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
-        case 3: return apply_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
-    }
-    return apply_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
-}
-
-// Launch plan: that of the Clenshaw kernels (make_clenshaw_plan: the one-step rule between the dictionary and
-// the streamed-block form, its tiles and its LDS) with the stored-source kernel in place of the probing one.
-struct ApplyPlan {
-    StepPlan step;
-    ApplyKernel kernel = nullptr;
-};
-
-int make_apply_plan(bdg_system* sys, int rl, const ModeInfo& mode, ApplyPlan* out) {
-    clenshaw_plan_shape(sys, rl, mode, &out->step);
-    out->kernel = apply_kernel(mode, out->step.dictionary, sys->max_row_blocks, rl);
-    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the stored-source Clenshaw kernels", rl);
-    return clenshaw_plan_launch(sys, reinterpret_cast<const void*>(out->kernel), &out->step);
-}
+using ApplyKernels = FamilyKernels<bdg::ApplyTail<false>, SharedDictKernels<bdg::ApplyTail<true>>>;
 
 // HBM bytes of one stored-source launch: a recurrence launch's matrix stream, and FOUR vector passes where it has
 // three (read b_{k+1}, b_{k+2} and x, write b_k), plus the launch's row of the coefficient table.
@@ -428,10 +143,8 @@ int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_fun
 
     // Real arithmetic whenever the matrix is real: the columns may be complex all the same (Re and Im in the two
     // slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
-    const char* real_env = knob::raw("BODGE_AMD_REAL");
-    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
-    const char* ph_env = knob::raw("BODGE_AMD_PH");
-    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const ModeInfo mode = family_mode(sys);
+    const bool real = mode.real;
     const int per_lane = mode.per_lane;
     // Columns per batch by the one-step width rule: the widest power of two whose vector buffer (16 B per entry
     // and column) stays within 96 MB, at most 64 columns - 32 in real arithmetic, whose kernels count a column as
@@ -441,8 +154,8 @@ int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_fun
     while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
     int rl = std::max(4, next_pow2((int)std::min<int64_t>(n_columns, width)));
     if (sys->lanes_override >= 4) rl = sys->lanes_override;
-    ApplyPlan aplan;
-    if (int rc = make_apply_plan(sys, rl, mode, &aplan)) return rc;
+    FamilyPlan<ApplyKernels::Kernel> aplan;
+    if (int rc = make_family_plan<ApplyKernels>(sys, rl, mode, 0, &aplan)) return rc;
     const StepPlan& plan = aplan.step;
     const int rv = rl * per_lane;
     bdg::StepArgs base{};
@@ -451,10 +164,9 @@ int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_fun
     if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
         return rc;
     const size_t vec_count = (size_t)4 * nb * rl;
-    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
-    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
-    bool alternate = true;
-    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const VectorHints hints = family_vector_hints(vec_count);
+    base.stream_vectors = hints.stream_vectors;
+    const bool alternate = hints.alternate;
     const int n_batches = (int)((n_columns + rl - 1) / rl);
 
     // Side by side on two of the handle's stream sets while one launch leaves the GPU part empty (the rule of
@@ -564,19 +276,7 @@ int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_fun
         perf.launches = (int64_t)n_batches * n_moments;
         perf.bytes_per_launch = apply_bytes(sys, rv, mode, plan.dictionary, n_functions);
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        perf.lanes_per_row = rl;
-        perf.vectors_per_launch = rv;
-        perf.grid = plan.grid;
-        perf.lds_bytes = (int32_t)plan.lds_footprint;
-        perf.pipelined = 0;
-        perf.real_arithmetic = real ? 1 : 0;
-        perf.strip_rows = strip_rows;
-        perf.ph_packed = mode.ph ? 1 : 0;
-        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
-        perf.steps_per_launch = 1;
-        perf.dict_skipped = sys->dict_skipped;
-        perf.streams = n_streams;
-        perf.groups_per_launch = 1;
+        family_perf(sys, plan, rv, strip_rows, n_streams, &perf);
         perf.apply = plan.dictionary ? 2 : 1;
         if (record) sys->perf = perf;
         return BDG_OK;

@@ -12,6 +12,8 @@
 //   plans.hpp       kernel dispatch tables, launch plans (one-step, sweeps, 3-D rolling), stencil tables
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
+//   family.hpp      the two tile loops, dispatch, launch plan and set-up shared by fermi / apply / correlation /
+//                   green / green_map / green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
 //   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver
@@ -59,6 +61,7 @@
 #include "plans.hpp"
 #include "libraries.hpp"
 #include "recurrence.hpp"
+#include "family.hpp"
 #include "fermi.hpp"
 #include "apply.hpp"
 #include "correlation.hpp"

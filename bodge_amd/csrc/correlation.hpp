@@ -234,10 +234,8 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
     HIP_TRY(hipSetDevice(sys->device));
 
     // Arithmetic mode and columns per batch as in run_apply_series.
-    const char* real_env = knob::raw("BODGE_AMD_REAL");
-    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
-    const char* ph_env = knob::raw("BODGE_AMD_PH");
-    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const ModeInfo mode = family_mode(sys);
+    const bool real = mode.real;
     const double per_column = (double)nb * 4 * 16.0;
     int width = real ? 32 : 64;
     while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
@@ -268,8 +266,8 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
     const int64_t n_slices = (K + slice - 1) / slice;
     if (n_slices > 65535) return fail(BDG_EINVAL, "BODGE_AMD_CORRELATION_SLICE = %d cuts a panel row into more than 65535 slices", slice);
 
-    ApplyPlan aplan;
-    if (int rc = make_apply_plan(sys, rl, mode, &aplan)) return rc;
+    FamilyPlan<ApplyKernels::Kernel> aplan;
+    if (int rc = make_family_plan<ApplyKernels>(sys, rl, mode, 0, &aplan)) return rc;
     const StepPlan& plan = aplan.step;
     const int rv = rl * mode.per_lane;
     bdg::StepArgs base{};
@@ -278,10 +276,9 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
     if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
         return rc;
     const size_t vec_count = (size_t)K;
-    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
-    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
-    bool alternate = true;
-    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const VectorHints hints = family_vector_hints(vec_count);
+    base.stream_vectors = hints.stream_vectors;
+    const bool alternate = hints.alternate;
     const int n_batches = (n_vectors + rl - 1) / rl;
 
     // start batch (kept: the X recurrence restarts from it), the two vector pairs, the caller's vectors of a batch
@@ -403,19 +400,7 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
         perf.kernel_ms = window;
         perf.bytes_per_launch = apply_bytes(sys, rv, mode, plan.dictionary, 1);
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        perf.lanes_per_row = rl;
-        perf.vectors_per_launch = rv;
-        perf.grid = plan.grid;
-        perf.lds_bytes = (int32_t)plan.lds_footprint;
-        perf.pipelined = 0;
-        perf.real_arithmetic = real ? 1 : 0;
-        perf.strip_rows = strip_rows;
-        perf.ph_packed = mode.ph ? 1 : 0;
-        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
-        perf.steps_per_launch = 1;
-        perf.dict_skipped = sys->dict_skipped;
-        perf.streams = 1;
-        perf.groups_per_launch = 1;
+        family_perf(sys, plan, rv, strip_rows, 1, &perf);
         perf.correlation = 1;
         sys->perf = perf;
         return BDG_OK;

@@ -45,114 +45,26 @@ __device__ inline void add_source(double2 nx[4], const ClenshawArgs& a, int colo
     }
 }
 
-// Generic form: cheb_step's tile loop (LDS staging of the streamed blocks, gathers of b_{k+1}) with the
-// Clenshaw epilogue b_k = coef * (H b_{k+1}) - b_{k+2} + c_k r.
-template <typename Mode, int RL>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw(ClenshawArgs ca) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ca.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int s = lane / RL;
-    const int r = lane % RL;
-    const int region = a.stage_blocks * STRIDE;
-    double2* stage = lds + wave * region;
-    const double2* all_blocks = static_cast<const double2*>(a.blocks);
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-
-    for (int t = t_lo + slot; t < t_hi; t += slots) {
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        const int row0 = (tile * kWavesPerBlock + wave) * RW;
-        if (row0 >= a.nb) continue;
-        const int row_end = min(row0 + RW, a.nb);
-        const int kb0 = a.indptr[row0];
-        const int kb1 = a.indptr[row_end];
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        int kbeg = 0, kend = 0, colour = -1;
-        if (valid) {
-            kbeg = a.indptr[i];
-            kend = a.indptr[i + 1];
-            colour = ca.site_colour[i];
-        }
-        double2 acc[4];
-#pragma unroll
-        for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-
-        for (int c0 = kb0; c0 < kb1; c0 += a.stage_blocks) {
-            const int c1 = min(c0 + a.stage_blocks, kb1);
-            const int n_el = (c1 - c0) * SPB;
-            const double2* src = all_blocks + (size_t)c0 * SPB;
-            for (int e0 = 0; e0 < n_el; e0 += 4 * kWave) {
-                double2 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) v[u] = load_stream(src + e);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) stage[(e / SPB) * STRIDE + (e % SPB)] = v[u];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-            const int k0 = max(kbeg, c0), k1 = min(kend, c1);
-            double2 x[4], xn[4];
-            if (k0 < k1) {
-                const size_t j = (size_t)a.indices[k0];
-#pragma unroll
-                for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-            }
-            for (int k = k0; k < k1; ++k) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                if (k + 1 < k1) {
-                    const size_t j = (size_t)a.indices[k + 1];
-#pragma unroll
-                    for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-                }
-                Mode::mac_row(acc, stage + (k - c0) * STRIDE, x);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
-
-        if (valid) {
-            double2 nx[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                const double2 p = (a.stream_vectors & 1) ? load_stream(a.prev + own) : a.prev[own];
-                nx[al].x = fma(a.coef, acc[al].x, -p.x);
-                nx[al].y = fma(a.coef, acc[al].y, -p.y);
-            }
-            add_source<Mode::kVec>(nx, ca, colour, r);
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
-                else a.prev[own] = nx[al];
-            }
-        }
+// The tail of the probing Clenshaw step b_k = coef * (H b_{k+1}) - b_{k+2} + c_k r on the shared streamed-block tile
+// loop (family.hpp): the colour of the block row, and the source term before the store.
+struct FermiTail : FamilyTail {
+    using Args = ClenshawArgs;
+    static constexpr const char* kFamily = "Clenshaw";
+    template <typename Mode, int RL>
+    __device__ static int row(const ClenshawArgs& ca, NoValue, int i) {
+        return ca.site_colour[i];
     }
-}
+    template <typename Mode, int RL>
+    __device__ static void amend(const ClenshawArgs& ca, int colour, int, int r, double2 nx[4], double2[4]) {
+        add_source<Mode::kVec>(nx, ca, colour, r);
+    }
+};
 
-// Dictionary form: cheb_step_dict's tile loop (block table in LDS, fixed-width row words, own and
-// neighbouring rows of b_{k+1} shared through LDS) with the Clenshaw epilogue.
+// Dictionary form: a tile loop of its own, the one the shared cheb_family_dict was lifted from (block table in LDS,
+// fixed-width row words, own and neighbouring rows of b_{k+1} shared through LDS) with the Clenshaw epilogue.  With
+// FermiTail on the shared loop this form was 4.5 % slower per launch on a cache-resident 256 x 256 lattice and 1.6 % on
+// a 1000 x 1000 one (profiles/family_tile_loop_ab.json), so it stays; the streamed-block form, within
+// the spread of the measurement on the shared loop, runs that.
 template <typename Mode, int RL, int MAXB>
 __global__ __launch_bounds__(kBlockThreads, 4) void cheb_clenshaw_dict(ClenshawArgs ca) {
     extern __shared__ double2 lds[];
@@ -330,102 +242,11 @@ __global__ void fermi_extract(const double2* __restrict__ y, int64_t nb, int rl,
 
 namespace {
 
-using ClenshawKernel = void (*)(bdg::ClenshawArgs);
-
-template <typename Mode>
-ClenshawKernel clenshaw_generic_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_clenshaw<Mode, 4>;
-        case 8: return bdg::cheb_clenshaw<Mode, 8>;
-        case 16: return bdg::cheb_clenshaw<Mode, 16>;
-        case 32: return bdg::cheb_clenshaw<Mode, 32>;
-        case 64: return bdg::cheb_clenshaw<Mode, 64>;
-    }
-    return nullptr;
-}
-
-template <typename Mode, int MAXB>
-ClenshawKernel clenshaw_dict_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_clenshaw_dict<Mode, 4, MAXB>;
-        case 8: return bdg::cheb_clenshaw_dict<Mode, 8, MAXB>;
-        case 16: return bdg::cheb_clenshaw_dict<Mode, 16, MAXB>;
-        case 32: return bdg::cheb_clenshaw_dict<Mode, 32, MAXB>;
-    }
-    // (64 lanes: complex modes only, as for the one-step dictionary kernel)
-    if constexpr (Mode::kVec == 1)
-        if (rl == 64) return bdg::cheb_clenshaw_dict<Mode, 64, MAXB>;
-    return nullptr;
-}
-
-template <typename Mode>
-ClenshawKernel clenshaw_kernel_for(bool dictionary, int max_row_blocks, int rl) {
-    if (!dictionary) return clenshaw_generic_for<Mode>(rl);
-    if (max_row_blocks <= 3) return clenshaw_dict_for<Mode, 3>(rl);
-    if (max_row_blocks <= 5) return clenshaw_dict_for<Mode, 5>(rl);
-    return clenshaw_dict_for<Mode, 7>(rl);
-}
-
-ClenshawKernel clenshaw_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
-    switch (mode.id) {
-        case 1: return clenshaw_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
-        case 2: return clenshaw_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
-        case 3: return clenshaw_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
-    }
-    return clenshaw_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
-}
-
-// Launch plan of the Clenshaw kernels: the one-step recurrence's choice between the dictionary and the
-// streamed-block form (dict_kernel decides, as in make_plan), its tiles and its LDS, without the space of the
-// dot reduction.  The pipelined one-step form has no Clenshaw twin: a matrix that would take it runs the
-// generic form.
-struct ClenshawPlan {
-    StepPlan step;  // tiles, grid, LDS, mode, dictionary flag (step.kernel unused)
-    ClenshawKernel kernel = nullptr;
+struct FermiDictKernels {
+    template <typename Mode, int RL, int MAXB>
+    static constexpr void (*kernel)(bdg::ClenshawArgs) = bdg::cheb_clenshaw_dict<Mode, RL, MAXB>;
 };
-
-// The two halves of that plan, shared with the stored-source kernels of apply.hpp: the shape (tiles, form) that the
-// kernel lookup needs, then LDS and grid for the kernel found.
-void clenshaw_plan_shape(const bdg_system* sys, int rl, const ModeInfo& mode, StepPlan* plan) {
-    *plan = StepPlan{};
-    plan->rl = rl;
-    plan->mode = mode;
-    const int rows_per_wave = bdg::kWave / rl;
-    plan->rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
-    plan->n_tiles = (int)((sys->nb + plan->rows_per_tile - 1) / plan->rows_per_tile);
-    plan->dictionary = dict_kernel(sys, mode, rl) != nullptr;
-}
-
-int clenshaw_plan_launch(const bdg_system* sys, const void* kernel, StepPlan* plan) {
-    const ModeInfo& mode = plan->mode;
-    const int rows_per_wave = bdg::kWave / plan->rl;
-    if (plan->dictionary) {
-        plan->lds_bytes = plan->lds_footprint = (size_t)sys->n_unique * mode.stride * sizeof(double2) +
-                                                (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
-    } else {
-        const int tile_blocks = rows_per_wave * std::max(1, sys->max_row_blocks);
-        const int cap = (int)((160 * 1024 / bdg::kWavesPerBlock) / (mode.stride * sizeof(double2)));
-        plan->stage_blocks = std::max(1, std::min(tile_blocks, cap));
-        plan->lds_bytes = plan->lds_footprint =
-            (size_t)bdg::kWavesPerBlock * plan->stage_blocks * mode.stride * sizeof(double2);
-        if (plan->lds_bytes > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan->lds_bytes));
-    }
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, bdg::kBlockThreads, plan->lds_bytes));
-    per_cu = std::max(1, std::min(per_cu, 8));
-    if (const char* cap = knob::raw("BODGE_AMD_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(cap));
-    const int grid = std::min(plan->n_tiles, per_cu * sys->num_cus);
-    plan->grid = std::max(8, (grid + 7) / 8 * 8);
-    return BDG_OK;
-}
-
-int make_clenshaw_plan(bdg_system* sys, int rl, const ModeInfo& mode, ClenshawPlan* out) {
-    clenshaw_plan_shape(sys, rl, mode, &out->step);
-    out->kernel = clenshaw_kernel(mode, out->step.dictionary, sys->max_row_blocks, rl);
-    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the Clenshaw kernels", rl);
-    return clenshaw_plan_launch(sys, reinterpret_cast<const void*>(out->kernel), &out->step);
-}
+using FermiKernels = FamilyKernels<bdg::FermiTail, FermiDictKernels>;
 
 // HBM bytes of one Clenshaw launch: a recurrence launch's (same matrix stream, same three vector passes)
 // plus the int32 colour of every block row.
@@ -478,10 +299,8 @@ int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double*
     }
 
     // Arithmetic and storage mode as for a recurrence with real start vectors (the probes are 0 / 1).
-    const char* real_env = knob::raw("BODGE_AMD_REAL");
-    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
-    const char* ph_env = knob::raw("BODGE_AMD_PH");
-    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const ModeInfo mode = family_mode(sys);
+    const bool real = mode.real;
     const int per_lane = mode.per_lane;
     // Vectors per batch: whole colours, the widest power of two up to 64 whose vector buffer stays within
     // 96 MB (batch_width's rule); set_lanes_per_row fixes the lanes instead.
@@ -495,8 +314,8 @@ int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double*
     int rl = std::max(4, next_pow2((n_active_max + per_lane - 1) / per_lane));
     if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= n_active_max) rl = sys->lanes_override;
     const int rv = rl * per_lane;
-    ClenshawPlan cplan;
-    if (int rc = make_clenshaw_plan(sys, rl, mode, &cplan)) return rc;
+    FamilyPlan<FermiKernels::Kernel> cplan;
+    if (int rc = make_family_plan<FermiKernels>(sys, rl, mode, 0, &cplan)) return rc;
     const StepPlan& plan = cplan.step;
     bdg::StepArgs base{};
     if (int rc = matrix_args(sys, plan, &base)) return rc;
@@ -505,10 +324,9 @@ int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double*
                                     &strip_rows))
         return rc;
     const size_t vec_count = (size_t)4 * nb * rl;
-    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
-    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
-    bool alternate = true;
-    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const VectorHints hints = family_vector_hints(vec_count);
+    base.stream_vectors = hints.stream_vectors;
+    const bool alternate = hints.alternate;
     const int n_batches = (n_colours + colours_per_batch - 1) / colours_per_batch;
 
     // Side by side on two of the handle's stream sets while one launch leaves the GPU part empty (the rule of
@@ -624,19 +442,7 @@ int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double*
         perf.launches = (int64_t)n_batches * n_moments;
         perf.bytes_per_launch = clenshaw_bytes(sys, rv, mode, plan.dictionary);
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        perf.lanes_per_row = rl;
-        perf.vectors_per_launch = rv;
-        perf.grid = plan.grid;
-        perf.lds_bytes = (int32_t)plan.lds_footprint;
-        perf.pipelined = 0;
-        perf.real_arithmetic = real ? 1 : 0;
-        perf.strip_rows = strip_rows;
-        perf.ph_packed = mode.ph ? 1 : 0;
-        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
-        perf.steps_per_launch = 1;
-        perf.dict_skipped = sys->dict_skipped;
-        perf.streams = n_streams;
-        perf.groups_per_launch = 1;
+        family_perf(sys, plan, rv, strip_rows, n_streams, &perf);
         perf.clenshaw = plan.dictionary ? 2 : 1;
         sys->perf = perf;
         return BDG_OK;

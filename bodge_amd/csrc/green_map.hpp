@@ -47,256 +47,16 @@ __device__ inline void store_local(const GreenLocalArgs& g, int position, int r,
     }
 }
 
-// Generic form: the twin of cheb_green (LDS staging of the streamed blocks, gathers of t_n, epilogue
-// t_{n+1} = coef * (H t_n) - t_{n-1}) with the store of the vectors' own rows.
-template <typename Mode, int RL>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_local(GreenLocalArgs ga) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ga.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int s = lane / RL;
-    const int r = lane % RL;
-    const int region = a.stage_blocks * STRIDE;
-    double2* stage = lds + wave * region;
-    const double2* all_blocks = static_cast<const double2*>(a.blocks);
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-
-    for (int t = t_lo + slot; t < t_hi; t += slots) {
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        const int row0 = (tile * kWavesPerBlock + wave) * RW;
-        if (row0 >= a.nb) continue;
-        const int row_end = min(row0 + RW, a.nb);
-        const int kb0 = a.indptr[row0];
-        const int kb1 = a.indptr[row_end];
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        int kbeg = 0, kend = 0;
-        if (valid) {
-            kbeg = a.indptr[i];
-            kend = a.indptr[i + 1];
-        }
-        double2 acc[4];
-#pragma unroll
-        for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-
-        for (int c0 = kb0; c0 < kb1; c0 += a.stage_blocks) {
-            const int c1 = min(c0 + a.stage_blocks, kb1);
-            const int n_el = (c1 - c0) * SPB;
-            const double2* src = all_blocks + (size_t)c0 * SPB;
-            for (int e0 = 0; e0 < n_el; e0 += 4 * kWave) {
-                double2 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) v[u] = load_stream(src + e);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) stage[(e / SPB) * STRIDE + (e % SPB)] = v[u];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-            const int k0 = max(kbeg, c0), k1 = min(kend, c1);
-            double2 x[4], xn[4];
-            if (k0 < k1) {
-                const size_t j = (size_t)a.indices[k0];
-#pragma unroll
-                for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-            }
-            for (int k = k0; k < k1; ++k) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                if (k + 1 < k1) {
-                    const size_t j = (size_t)a.indices[k + 1];
-#pragma unroll
-                    for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-                }
-                Mode::mac_row(acc, stage + (k - c0) * STRIDE, x);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
-
-        if (valid) {
-            double2 nx[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                const double2 p = (a.stream_vectors & 1) ? load_stream(a.prev + own) : a.prev[own];
-                nx[al].x = fma(a.coef, acc[al].x, -p.x);
-                nx[al].y = fma(a.coef, acc[al].y, -p.y);
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
-                else a.prev[own] = nx[al];
-            }
-            // (the position is read here, after the tile loop and the vector stores: nothing of it is live before)
-            store_local<Mode::kVec>(ga, ga.site_slot[i], r, nx);
-        }
+// The tail of the full-width picked step on the shared tile loops (family.hpp): after the store of t_{n+1}, the
+// store of the vectors' own rows.  The site slot is read there and nowhere earlier.
+struct GreenLocalTail : FamilyTail {
+    using Args = GreenLocalArgs;
+    static constexpr const char* kFamily = "picked recurrence";
+    template <typename Mode, int RL>
+    __device__ static void after(const GreenLocalArgs& ga, NoValue, NoValue, int i, int r, const double2 nx[4]) {
+        store_local<Mode::kVec>(ga, ga.site_slot[i], r, nx);
     }
-}
-
-// Dictionary form: the twin of cheb_green_dict (block table in LDS, fixed-width row words, own and
-// neighbouring rows of t_n shared through LDS) with the same epilogue.
-template <typename Mode, int RL, int MAXB>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_local_dict(GreenLocalArgs ga) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ga.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int s = lane / RL;
-    const int r = lane % RL;
-
-    const double2* table = static_cast<const double2*>(a.dict_table);
-    for (int e = threadIdx.x; e < a.n_unique * SPB; e += kBlockThreads)
-        lds[(e / SPB) * STRIDE + (e % SPB)] = table[e];
-    double2* share = lds + a.n_unique * STRIDE + wave * (kWave * 4);
-    __syncthreads();
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-    auto first_row = [&](int t) {
-        if (t >= t_hi) return a.nb;
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        return (tile * kWavesPerBlock + wave) * RW;
-    };
-    struct RowMeta {
-        int len;
-        unsigned word[MAXB];
-    };
-    auto col_of = [](unsigned w) { return (size_t)(w & 0xFFFFFFu); };
-    auto id_of = [](unsigned w) { return (int)(w >> 24); };
-    constexpr int ELLW = MAXB <= 3 ? 4 : 8;
-    auto load_meta = [&](int row0, RowMeta& m) {
-        const int i = row0 + s;
-        const uint4* src = reinterpret_cast<const uint4*>(a.dict_ell) + (size_t)min(i, a.nb - 1) * (ELLW / 4);
-        unsigned words[8];
-        const uint4 lo = src[0];
-        words[0] = lo.x, words[1] = lo.y, words[2] = lo.z, words[3] = lo.w;
-        if constexpr (ELLW == 8) {
-            const uint4 hi = src[1];
-            words[4] = hi.x, words[5] = hi.y, words[6] = hi.z, words[7] = hi.w;
-        } else {
-            words[4] = words[5] = words[6] = words[7] = 0xFFFFFFFFu;
-        }
-        m.len = 0;
-#pragma unroll
-        for (int q = 0; q < MAXB; ++q) {
-            const bool there = i < a.nb && words[q] != 0xFFFFFFFFu;
-            m.len += there ? 1 : 0;
-            m.word[q] = there ? words[q] : 0u;
-        }
-    };
-
-    int pos = t_lo + slot;
-    int row0 = first_row(pos);
-    RowMeta meta;
-    load_meta(row0, meta);
-    for (; pos < t_hi; pos += slots) {
-        const int row0_n = first_row(pos + slots);
-        RowMeta meta_n;
-        load_meta(row0_n, meta_n);
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        {
-            double2 own[4];
-#pragma unroll
-            for (int be = 0; be < 4; ++be)
-                own[be] = valid ? a.cur[vslot(be, (size_t)i, r, a.ncols, RL)] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int be = 0; be < 4; ++be) share[SHARE_SLOT(lane, be)] = own[be];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-        if (valid) {
-            auto source = [&](unsigned w) {
-                const long d = (long)col_of(w) - (long)i;
-                const long ss = (long)s + d;
-                return (ss >= 0 && ss < RW && (long)i + d < a.nb) ? (int)d : (int)kWave;
-            };
-            double2 acc[4], x[4], xn[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-            if (meta.len > 0 && source(meta.word[0]) == kWave) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be)
-                    xn[be] = a.cur[vslot(be, col_of(meta.word[0]), r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int q = 0; q < MAXB; ++q) {
-                if (q < meta.len) {
-                    const int src = source(meta.word[q]);
-                    if (src == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                    } else {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = share[SHARE_SLOT(lane + src * RL, be)];
-                    }
-                    if (q + 1 < MAXB && q + 1 < meta.len && source(meta.word[q + 1 < MAXB ? q + 1 : 0]) == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be)
-                            xn[be] = a.cur[vslot(be, col_of(meta.word[q + 1 < MAXB ? q + 1 : 0]), r, a.ncols, RL)];
-                    }
-                    Mode::mac_row(acc, lds + id_of(meta.word[q]) * STRIDE, x);
-                }
-            }
-            double2 p[4];
-            if (a.stream_vectors & 1) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = load_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL));
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = a.prev[vslot(al, (size_t)i, r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                p[al].x = fma(a.coef, acc[al].x, -p[al].x);
-                p[al].y = fma(a.coef, acc[al].y, -p[al].y);
-            }
-            if (a.stream_vectors & 2) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) store_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL), p[al]);
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) a.prev[vslot(al, (size_t)i, r, a.ncols, RL)] = p[al];
-            }
-            // (the position is read in the epilogue, not before the tile's products: one live register less across them)
-            store_local<Mode::kVec>(ga, ga.site_slot[i], r, p);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        row0 = row0_n;
-        meta = meta_n;
-    }
-}
+};
 
 // Moment 0 from the start vectors themselves: table[s][al][b] = t_0[al][rows[s]][(s << comp_shift) + b], with
 // the vector index counted inside the batch.  One thread per entry.  PER_LANE = 2: real payloads, vector v in
@@ -320,50 +80,7 @@ __global__ void green_local_pick(const double2* __restrict__ vec, int64_t nb, in
 
 namespace {
 
-using GreenLocalKernel = void (*)(bdg::GreenLocalArgs);
-
-template <typename Mode>
-GreenLocalKernel green_local_generic_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_green_local<Mode, 4>;
-        case 8: return bdg::cheb_green_local<Mode, 8>;
-        case 16: return bdg::cheb_green_local<Mode, 16>;
-        case 32: return bdg::cheb_green_local<Mode, 32>;
-        case 64: return bdg::cheb_green_local<Mode, 64>;
-    }
-    return nullptr;
-}
-
-template <typename Mode, int MAXB>
-GreenLocalKernel green_local_dict_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_green_local_dict<Mode, 4, MAXB>;
-        case 8: return bdg::cheb_green_local_dict<Mode, 8, MAXB>;
-        case 16: return bdg::cheb_green_local_dict<Mode, 16, MAXB>;
-        case 32: return bdg::cheb_green_local_dict<Mode, 32, MAXB>;
-    }
-    // (64 lanes: complex modes only, as for the Clenshaw dictionary kernel)
-    if constexpr (Mode::kVec == 1)
-        if (rl == 64) return bdg::cheb_green_local_dict<Mode, 64, MAXB>;
-    return nullptr;
-}
-
-template <typename Mode>
-GreenLocalKernel green_local_kernel_for(bool dictionary, int max_row_blocks, int rl) {
-    if (!dictionary) return green_local_generic_for<Mode>(rl);
-    if (max_row_blocks <= 3) return green_local_dict_for<Mode, 3>(rl);
-    if (max_row_blocks <= 5) return green_local_dict_for<Mode, 5>(rl);
-    return green_local_dict_for<Mode, 7>(rl);
-}
-
-GreenLocalKernel green_local_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
-    switch (mode.id) {
-        case 1: return green_local_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
-        case 2: return green_local_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
-        case 3: return green_local_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
-    }
-    return green_local_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
-}
+using GreenLocalKernels = FamilyKernels<bdg::GreenLocalTail>;
 
 int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_sites, const int32_t* block_rows,
                             int n_components, double* out) {
@@ -391,10 +108,8 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
     HIP_TRY(hipSetDevice(sys->device));
 
     // Arithmetic and storage mode as for a recurrence with unit start vectors.
-    const char* real_env = knob::raw("BODGE_AMD_REAL");
-    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
-    const char* ph_env = knob::raw("BODGE_AMD_PH");
-    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const ModeInfo mode = family_mode(sys);
+    const bool real = mode.real;
     const int per_lane = mode.per_lane;
     // Vectors per batch: the widest power of two up to 64 whose vector buffer stays within 96 MB (batch_width's
     // rule for the one-step kernels); set_lanes_per_row fixes the lanes instead.  A batch holds whole sites.
@@ -407,8 +122,8 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
     if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= width) rl = sys->lanes_override;
     const int rv = rl * per_lane;
     const int batch_sites = width / n_components;
-    PickedPlan<GreenLocalKernel> gplan;
-    if (int rc = make_picked_plan(sys, rl, mode, green_local_kernel, &gplan)) return rc;
+    FamilyPlan<GreenLocalKernels::Kernel> gplan;
+    if (int rc = make_family_plan<GreenLocalKernels>(sys, rl, mode, 0, &gplan)) return rc;
     const StepPlan& plan = gplan.step;
     bdg::StepArgs base{};
     if (int rc = matrix_args(sys, plan, &base)) return rc;
@@ -417,10 +132,9 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
                                     &strip_rows))
         return rc;
     const size_t vec_count = (size_t)4 * nb * rl;
-    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
-    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
-    bool alternate = true;
-    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const VectorHints hints = family_vector_hints(vec_count);
+    base.stream_vectors = hints.stream_vectors;
+    const bool alternate = hints.alternate;
     const int n_batches = (n_sites + batch_sites - 1) / batch_sites;
 
     // Device table: [moment of the range][site of the batch][component][column]; a range of moments whose
@@ -523,19 +237,7 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
         perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 4.0 * (double)nb +
                                 (double)(per_moment_max * sizeof(double2));
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        perf.lanes_per_row = rl;
-        perf.vectors_per_launch = rv;
-        perf.grid = plan.grid;
-        perf.lds_bytes = (int32_t)plan.lds_footprint;
-        perf.pipelined = 0;
-        perf.real_arithmetic = real ? 1 : 0;
-        perf.strip_rows = strip_rows;
-        perf.ph_packed = mode.ph ? 1 : 0;
-        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
-        perf.steps_per_launch = 1;
-        perf.dict_skipped = sys->dict_skipped;
-        perf.streams = 1;
-        perf.groups_per_launch = 1;
+        family_perf(sys, plan, rv, strip_rows, 1, &perf);
         perf.green_ranges = n_ranges;
         perf.green_local = plan.dictionary ? 2 : 1;
         sys->perf = perf;

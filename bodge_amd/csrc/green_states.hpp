@@ -48,7 +48,7 @@ __device__ inline void project_state(double proj[8], const double2 w, const doub
 // the eight doubles made the streamed-block form spill in every mode (20 - 68 bytes per lane) and the dictionary form
 // in ComplexPHMode; in LDS they cost eight 16-byte LDS accesses per tile and no register.
 // The lane's slot is worked out where it is used, from an index the compiler cannot see through: kept across the
-// tile loop it was the one register too many of cheb_green_state<ComplexPHMode> (12 bytes of scratch per lane with
+// tile loop it was the one register too many of the streamed-block form in ComplexPHMode (12 bytes of scratch per lane with
 // hipcc of ROCm 7.2.0, AMD clang 22.0.0git; tests/test_green_states_host.py pins scratch = 0 for every instance).
 __device__ inline double2* projection_slot(double2* rows) {
     int tid = threadIdx.x;
@@ -103,270 +103,34 @@ __device__ inline void reduce_projection(double proj[8], double* red, double* pa
     }
 }
 
-// Generic form: the twin of cheb_green_local (LDS staging of the streamed blocks, gathers of t_n, epilogue
-// t_{n+1} = coef * (H t_n) - t_{n-1}) with the projection on the state in place of the picked store.
-template <typename Mode, int RL>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_state(GreenStateArgs ga) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ga.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x / kWave;
-    const int s = lane / RL;
-    const int r = lane % RL;
-    const int region = a.stage_blocks * STRIDE;
-    double2* stage = lds + wave * region;
-    double2* accum = lds + kWavesPerBlock * region;  // a row per wave, behind the staging regions of the four waves
-    const double2* all_blocks = static_cast<const double2*>(a.blocks);
-    clear_projection(accum);
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-
-    for (int t = t_lo + slot; t < t_hi; t += slots) {
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        const int row0 = (tile * kWavesPerBlock + wave) * RW;
-        if (row0 >= a.nb) continue;
-        const int row_end = min(row0 + RW, a.nb);
-        const int kb0 = a.indptr[row0];
-        const int kb1 = a.indptr[row_end];
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        int kbeg = 0, kend = 0;
-        if (valid) {
-            kbeg = a.indptr[i];
-            kend = a.indptr[i + 1];
-        }
-        double2 acc[4];
-#pragma unroll
-        for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-
-        for (int c0 = kb0; c0 < kb1; c0 += a.stage_blocks) {
-            const int c1 = min(c0 + a.stage_blocks, kb1);
-            const int n_el = (c1 - c0) * SPB;
-            const double2* src = all_blocks + (size_t)c0 * SPB;
-            for (int e0 = 0; e0 < n_el; e0 += 4 * kWave) {
-                double2 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) v[u] = load_stream(src + e);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = e0 + u * kWave + lane;
-                    if (e < n_el) stage[(e / SPB) * STRIDE + (e % SPB)] = v[u];
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-            const int k0 = max(kbeg, c0), k1 = min(kend, c1);
-            double2 x[4], xn[4];
-            if (k0 < k1) {
-                const size_t j = (size_t)a.indices[k0];
-#pragma unroll
-                for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-            }
-            for (int k = k0; k < k1; ++k) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                if (k + 1 < k1) {
-                    const size_t j = (size_t)a.indices[k + 1];
-#pragma unroll
-                    for (int be = 0; be < 4; ++be) xn[be] = a.cur[vslot(be, j, r, a.ncols, RL)];
-                }
-                Mode::mac_row(acc, stage + (k - c0) * STRIDE, x);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-        }
-
-        if (valid) {
-            double2 nx[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                const double2 p = (a.stream_vectors & 1) ? load_stream(a.prev + own) : a.prev[own];
-                nx[al].x = fma(a.coef, acc[al].x, -p.x);
-                nx[al].y = fma(a.coef, acc[al].y, -p.y);
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                const size_t own = vslot(al, (size_t)i, r, a.ncols, RL);
-                if (a.stream_vectors & 2) store_stream(a.prev + own, nx[al]);
-                else a.prev[own] = nx[al];
-            }
-            // (the amplitude is read here, after the tile's products and the vector stores: nothing of it is live before)
-            project_state_lds(accum, state_amplitude(ga, r, i), nx);
-        }
+// The tail of the projected step on the shared tile loops (family.hpp): the accumulators of the projection lie in
+// the LDS behind what the tile loop uses (the staging regions in the streamed-block form, the shared rows in the
+// dictionary form), a row per wave; after the store of t_{n+1} the lane adds its products, and after the tile loop
+// the workgroup reduces them.
+struct GreenStateTail : FamilyTail {
+    using Args = GreenStateArgs;
+    static constexpr const char* kFamily = "projected recurrence";
+    // the accumulators: four 16-byte slots per lane (16 KB).  The reduction of the eight doubles per lane
+    // (kWavesPerBlock * RL * 8 doubles <= 16 KB) reuses the front of the LDS.
+    static constexpr size_t kExtraLds = (size_t)kBlockThreads * 4 * sizeof(double2);
+    template <typename Mode, int RL>
+    __device__ static double2* begin(const GreenStateArgs&, int, double2* behind) {
+        clear_projection(behind);
+        return behind;
     }
-
-    double proj[8];
-    load_projection(accum, proj);
-    __syncthreads();  // every wave is done with its staging region and its accumulators: the reduction reuses the front of the LDS
-    reduce_projection<RL>(proj, reinterpret_cast<double*>(lds), ga.partial, lane, wave);
-}
-
-// Dictionary form: the twin of cheb_green_local_dict (block table in LDS, fixed-width row words, own and
-// neighbouring rows of t_n shared through LDS) with the same epilogue.
-template <typename Mode, int RL, int MAXB>
-__global__ __launch_bounds__(kBlockThreads, 4) void cheb_green_state_dict(GreenStateArgs ga) {
-    extern __shared__ double2 lds[];
-    const StepArgs& a = ga.s;
-    constexpr int RW = kWave / RL;
-    constexpr int SPB = Mode::kSlotsPerBlock;
-    constexpr int STRIDE = Mode::kBlockStride;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    const int s = lane / RL;
-    const int r = lane % RL;
-
-    const double2* table = static_cast<const double2*>(a.dict_table);
-    for (int e = threadIdx.x; e < a.n_unique * SPB; e += kBlockThreads)
-        lds[(e / SPB) * STRIDE + (e % SPB)] = table[e];
-    double2* share = lds + a.n_unique * STRIDE + wave * (kWave * 4);
-    double2* accum = lds + a.n_unique * STRIDE + kWavesPerBlock * (kWave * 4);  // a row per wave, behind the shared rows
-    clear_projection(accum);
-    __syncthreads();
-
-    const int xcd = blockIdx.x & 7;
-    const int slot = blockIdx.x >> 3;
-    const int slots = gridDim.x >> 3;
-    const int t_lo = (int)(((int64_t)a.n_tiles * xcd) >> 3);
-    const int t_hi = (int)(((int64_t)a.n_tiles * (xcd + 1)) >> 3);
-    auto first_row = [&](int t) {
-        if (t >= t_hi) return a.nb;
-        const int tt = a.reverse ? t_lo + t_hi - 1 - t : t;
-        const int tile = a.tile_order ? a.tile_order[tt] : tt + a.tile_base;
-        return (tile * kWavesPerBlock + wave) * RW;
-    };
-    struct RowMeta {
-        int len;
-        unsigned word[MAXB];
-    };
-    auto col_of = [](unsigned w) { return (size_t)(w & 0xFFFFFFu); };
-    auto id_of = [](unsigned w) { return (int)(w >> 24); };
-    constexpr int ELLW = MAXB <= 3 ? 4 : 8;
-    auto load_meta = [&](int row0, RowMeta& m) {
-        const int i = row0 + s;
-        const uint4* src = reinterpret_cast<const uint4*>(a.dict_ell) + (size_t)min(i, a.nb - 1) * (ELLW / 4);
-        unsigned words[8];
-        const uint4 lo = src[0];
-        words[0] = lo.x, words[1] = lo.y, words[2] = lo.z, words[3] = lo.w;
-        if constexpr (ELLW == 8) {
-            const uint4 hi = src[1];
-            words[4] = hi.x, words[5] = hi.y, words[6] = hi.z, words[7] = hi.w;
-        } else {
-            words[4] = words[5] = words[6] = words[7] = 0xFFFFFFFFu;
-        }
-        m.len = 0;
-#pragma unroll
-        for (int q = 0; q < MAXB; ++q) {
-            const bool there = i < a.nb && words[q] != 0xFFFFFFFFu;
-            m.len += there ? 1 : 0;
-            m.word[q] = there ? words[q] : 0u;
-        }
-    };
-
-    int pos = t_lo + slot;
-    int row0 = first_row(pos);
-    RowMeta meta;
-    load_meta(row0, meta);
-    for (; pos < t_hi; pos += slots) {
-        const int row0_n = first_row(pos + slots);
-        RowMeta meta_n;
-        load_meta(row0_n, meta_n);
-
-        const int i = row0 + s;
-        const bool valid = i < a.nb;
-        {
-            double2 own[4];
-#pragma unroll
-            for (int be = 0; be < 4; ++be)
-                own[be] = valid ? a.cur[vslot(be, (size_t)i, r, a.ncols, RL)] : make_double2(0.0, 0.0);
-#pragma unroll
-            for (int be = 0; be < 4; ++be) share[SHARE_SLOT(lane, be)] = own[be];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-        if (valid) {
-            auto source = [&](unsigned w) {
-                const long d = (long)col_of(w) - (long)i;
-                const long ss = (long)s + d;
-                return (ss >= 0 && ss < RW && (long)i + d < a.nb) ? (int)d : (int)kWave;
-            };
-            double2 acc[4], x[4], xn[4];
-#pragma unroll
-            for (int al = 0; al < 4; ++al) acc[al] = make_double2(0.0, 0.0);
-            if (meta.len > 0 && source(meta.word[0]) == kWave) {
-#pragma unroll
-                for (int be = 0; be < 4; ++be)
-                    xn[be] = a.cur[vslot(be, col_of(meta.word[0]), r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int q = 0; q < MAXB; ++q) {
-                if (q < meta.len) {
-                    const int src = source(meta.word[q]);
-                    if (src == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = xn[be];
-                    } else {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be) x[be] = share[SHARE_SLOT(lane + src * RL, be)];
-                    }
-                    if (q + 1 < MAXB && q + 1 < meta.len && source(meta.word[q + 1 < MAXB ? q + 1 : 0]) == kWave) {
-#pragma unroll
-                        for (int be = 0; be < 4; ++be)
-                            xn[be] = a.cur[vslot(be, col_of(meta.word[q + 1 < MAXB ? q + 1 : 0]), r, a.ncols, RL)];
-                    }
-                    Mode::mac_row(acc, lds + id_of(meta.word[q]) * STRIDE, x);
-                }
-            }
-            double2 p[4];
-            if (a.stream_vectors & 1) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = load_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL));
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) p[al] = a.prev[vslot(al, (size_t)i, r, a.ncols, RL)];
-            }
-#pragma unroll
-            for (int al = 0; al < 4; ++al) {
-                p[al].x = fma(a.coef, acc[al].x, -p[al].x);
-                p[al].y = fma(a.coef, acc[al].y, -p[al].y);
-            }
-            if (a.stream_vectors & 2) {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) store_stream(a.prev + vslot(al, (size_t)i, r, a.ncols, RL), p[al]);
-            } else {
-#pragma unroll
-                for (int al = 0; al < 4; ++al) a.prev[vslot(al, (size_t)i, r, a.ncols, RL)] = p[al];
-            }
-            // (the amplitude is read in the epilogue, not before the tile's products: two live registers less across them)
-            project_state_lds(accum, state_amplitude(ga, r, i), p);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        row0 = row0_n;
-        meta = meta_n;
+    template <typename Mode, int RL>
+    __device__ static void after(const GreenStateArgs& ga, double2* accum, NoValue, int i, int r, const double2 nx[4]) {
+        // (the amplitude is read here, after the tile's products and the vector stores: nothing of it is live before)
+        project_state_lds(accum, state_amplitude(ga, r, i), nx);
     }
-
-    double proj[8];
-    load_projection(accum, proj);
-    __syncthreads();  // table / share reads finished, accumulators in registers: the reduction reuses the front of the LDS
-    reduce_projection<RL>(proj, reinterpret_cast<double*>(lds), ga.partial, lane, wave);
-}
+    template <typename Mode, int RL>
+    __device__ static void finish(const GreenStateArgs& ga, double2* accum, double2* lds, int lane, int wave) {
+        double proj[8];
+        load_projection(accum, proj);
+        __syncthreads();  // every wave is done with the tile loop's LDS and its accumulators: the reduction reuses the front
+        reduce_projection<RL>(proj, reinterpret_cast<double*>(lds), ga.partial, lane, wave);
+    }
+};
 
 // t_0 of a batch from the amplitude table: t_0[4i + a][C q + b] = w_q[i] * delta_ab; the components a >= C and the
 // padding columns are zero.  Writes every payload of the buffer (no zero fill before it).
@@ -452,50 +216,7 @@ __global__ __launch_bounds__(256) void green_state_reduce(const double2* __restr
 
 namespace {
 
-using GreenStateKernel = void (*)(bdg::GreenStateArgs);
-
-template <typename Mode>
-GreenStateKernel green_state_generic_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_green_state<Mode, 4>;
-        case 8: return bdg::cheb_green_state<Mode, 8>;
-        case 16: return bdg::cheb_green_state<Mode, 16>;
-        case 32: return bdg::cheb_green_state<Mode, 32>;
-        case 64: return bdg::cheb_green_state<Mode, 64>;
-    }
-    return nullptr;
-}
-
-template <typename Mode, int MAXB>
-GreenStateKernel green_state_dict_for(int rl) {
-    switch (rl) {
-        case 4: return bdg::cheb_green_state_dict<Mode, 4, MAXB>;
-        case 8: return bdg::cheb_green_state_dict<Mode, 8, MAXB>;
-        case 16: return bdg::cheb_green_state_dict<Mode, 16, MAXB>;
-        case 32: return bdg::cheb_green_state_dict<Mode, 32, MAXB>;
-    }
-    // (64 lanes: complex modes only, as for the other dictionary kernels)
-    if constexpr (Mode::kVec == 1)
-        if (rl == 64) return bdg::cheb_green_state_dict<Mode, 64, MAXB>;
-    return nullptr;
-}
-
-template <typename Mode>
-GreenStateKernel green_state_kernel_for(bool dictionary, int max_row_blocks, int rl) {
-    if (!dictionary) return green_state_generic_for<Mode>(rl);
-    if (max_row_blocks <= 3) return green_state_dict_for<Mode, 3>(rl);
-    if (max_row_blocks <= 5) return green_state_dict_for<Mode, 5>(rl);
-    return green_state_dict_for<Mode, 7>(rl);
-}
-
-GreenStateKernel green_state_kernel(const ModeInfo& mode, bool dictionary, int max_row_blocks, int rl) {
-    switch (mode.id) {
-        case 1: return green_state_kernel_for<RealMode>(dictionary, max_row_blocks, rl);
-        case 2: return green_state_kernel_for<ComplexPHMode>(dictionary, max_row_blocks, rl);
-        case 3: return green_state_kernel_for<RealPHMode>(dictionary, max_row_blocks, rl);
-    }
-    return green_state_kernel_for<ComplexMode>(dictionary, max_row_blocks, rl);
-}
+using GreenStateKernels = FamilyKernels<bdg::GreenStateTail>;
 
 using GreenProjectKernel = void (*)(const double2*, int, int, int, const double2*, double*);
 
@@ -508,44 +229,6 @@ GreenProjectKernel green_state_project_for(int rl) {
         case 64: return bdg::green_state_project<64>;
     }
     return nullptr;
-}
-
-// Launch plan: that of the picked steps (make_picked_plan: the one-step rule between the dictionary and the
-// streamed-block form, its tiles) with an LDS request that also holds the accumulators of the projection.
-int make_green_state_plan(bdg_system* sys, int rl, const ModeInfo& mode, PickedPlan<GreenStateKernel>* out) {
-    StepPlan& plan = out->step;
-    plan = StepPlan{};
-    plan.rl = rl;
-    plan.mode = mode;
-    const int rows_per_wave = bdg::kWave / rl;
-    plan.rows_per_tile = rows_per_wave * bdg::kWavesPerBlock;
-    plan.n_tiles = (int)((sys->nb + plan.rows_per_tile - 1) / plan.rows_per_tile);
-    plan.dictionary = dict_kernel(sys, mode, rl) != nullptr;
-    out->kernel = green_state_kernel(mode, plan.dictionary, sys->max_row_blocks, rl);
-    if (!out->kernel) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the projected recurrence kernels", rl);
-    // the accumulators: four 16-byte slots per lane (16 KB), behind the table and shared rows / the staging regions.  The
-    // reduction of the eight doubles per lane (kWavesPerBlock * rl * 8 doubles <= 16 KB) reuses the front of the LDS.
-    const size_t accum = (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
-    if (plan.dictionary) {
-        plan.lds_bytes = (size_t)sys->n_unique * mode.stride * sizeof(double2) + (size_t)bdg::kBlockThreads * 4 * sizeof(double2);
-    } else {
-        const int tile_blocks = rows_per_wave * std::max(1, sys->max_row_blocks);
-        const int cap = (int)(((160 * 1024 - accum) / bdg::kWavesPerBlock) / (mode.stride * sizeof(double2)));
-        plan.stage_blocks = std::max(1, std::min(tile_blocks, cap));
-        plan.lds_bytes = (size_t)bdg::kWavesPerBlock * plan.stage_blocks * mode.stride * sizeof(double2);
-    }
-    plan.lds_bytes = plan.lds_footprint = plan.lds_bytes + accum;
-    if (plan.lds_bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(out->kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)plan.lds_bytes));
-    int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(out->kernel),
-                                                         bdg::kBlockThreads, plan.lds_bytes));
-    per_cu = std::max(1, std::min(per_cu, 8));
-    if (const char* cap = knob::raw("BODGE_AMD_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(cap));
-    const int grid = std::min(plan.n_tiles, per_cu * sys->num_cus);
-    plan.grid = std::max(8, (grid + 7) / 8 * 8);
-    return BDG_OK;
 }
 
 int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_states, const double* amplitudes,
@@ -565,10 +248,8 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
 
     // Arithmetic as for apply(): real whenever the matrix is real, the columns complex all the same (Re and Im in
     // the two slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
-    const char* real_env = knob::raw("BODGE_AMD_REAL");
-    const bool real = sys->is_real && !(real_env && real_env[0] == '0');
-    const char* ph_env = knob::raw("BODGE_AMD_PH");
-    const ModeInfo mode = mode_info(real, sys->is_ph && !(ph_env && ph_env[0] == '0'));
+    const ModeInfo mode = family_mode(sys);
+    const bool real = mode.real;
     const int per_lane = mode.per_lane;
     // Columns per batch by the width rule of run_apply_series: the widest power of two whose vector buffer stays
     // within 96 MB, at most 64 columns - 32 in real arithmetic; set_lanes_per_row fixes the lanes instead.  A batch
@@ -580,8 +261,8 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
     if (sys->lanes_override >= 4) rl = sys->lanes_override;
     const int rv = rl * per_lane;
     const int batch_states = rl / n_components;
-    PickedPlan<GreenStateKernel> gplan;
-    if (int rc = make_green_state_plan(sys, rl, mode, &gplan)) return rc;
+    FamilyPlan<GreenStateKernels::Kernel> gplan;
+    if (int rc = make_family_plan<GreenStateKernels>(sys, rl, mode, bdg::GreenStateTail::kExtraLds, &gplan)) return rc;
     const GreenProjectKernel project = green_state_project_for(rl);
     if (!project) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the projected recurrence kernels", rl);
     const StepPlan& plan = gplan.step;
@@ -591,10 +272,9 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
     if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
         return rc;
     const size_t vec_count = (size_t)4 * nb * rl;
-    base.stream_vectors = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 3 : 0;
-    if (const char* env = knob::raw("BODGE_AMD_STREAM_VECTORS")) base.stream_vectors = std::atoi(env);
-    bool alternate = true;
-    if (const char* env = knob::raw("BODGE_AMD_ALTERNATE")) alternate = std::atoi(env) != 0;
+    const VectorHints hints = family_vector_hints(vec_count);
+    base.stream_vectors = hints.stream_vectors;
+    const bool alternate = hints.alternate;
     const int n_batches = (n_states + batch_states - 1) / batch_states;
 
     // Device tables of a range of moments: the workgroups' partials [moment][workgroup][column][component] and the
@@ -689,19 +369,7 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
         perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 16.0 * (double)nb * batch_states +
                                 (double)(partial_entries * sizeof(double2));
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        perf.lanes_per_row = rl;
-        perf.vectors_per_launch = rv;
-        perf.grid = plan.grid;
-        perf.lds_bytes = (int32_t)plan.lds_footprint;
-        perf.pipelined = 0;
-        perf.real_arithmetic = real ? 1 : 0;
-        perf.strip_rows = strip_rows;
-        perf.ph_packed = mode.ph ? 1 : 0;
-        perf.dict_blocks = plan.dictionary ? sys->n_unique : 0;
-        perf.steps_per_launch = 1;
-        perf.dict_skipped = sys->dict_skipped;
-        perf.streams = 1;
-        perf.groups_per_launch = 1;
+        family_perf(sys, plan, rv, strip_rows, 1, &perf);
         perf.green_ranges = n_ranges;
         perf.green_states = plan.dictionary ? 2 : 1;
         sys->perf = perf;

@@ -288,7 +288,7 @@ def resources():
 def _row(resources, name):
     # (c++filt prints the return type of template instances only)
     matches = [row for key, row in resources.items() if key.startswith((f"void bdg::{name}(", f"bdg::{name}("))]
-    assert len(matches) == 1, (name, [k for k in resources if "clenshaw_vec" in k][:8])
+    assert len(matches) == 1, (name, [k for k in resources if "apply" in k][:8])
     return matches[0]
 
 
@@ -301,12 +301,12 @@ def test_stored_source_kernels_do_not_spill_and_keep_their_occupancy(resources):
     expected = set()
     for mode in ("RealPHMode", "ComplexPHMode", "RealMode", "ComplexMode"):
         for rl in (4, 8, 16, 32, 64):
-            expected.add(f"void bdg::cheb_clenshaw_vec<bdg::{mode}, {rl}>(bdg::ApplyArgs)")
+            expected.add(f"void bdg::cheb_family<bdg::{mode}, {rl}, bdg::ApplyTail<false> >(bdg::ApplyTail<false>::Args)")
             if rl == 64 and mode.startswith("Real"):
                 continue
             for maxb in (3, 5, 7):
-                expected.add(f"void bdg::cheb_clenshaw_vec_dict<bdg::{mode}, {rl}, {maxb}>(bdg::ApplyArgs)")
-    found = {key: row for key, row in resources.items() if "cheb_clenshaw_vec" in key}
+                expected.add(f"void bdg::cheb_family_dict<bdg::{mode}, {rl}, {maxb}, bdg::ApplyTail<true> >(bdg::ApplyTail<true>::Args)")
+    found = {key: row for key, row in resources.items() if "bdg::ApplyTail" in key}
     assert set(found) == expected and len(found) == 74, sorted(set(found) ^ expected)
     for key, row in found.items():
         assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (key, row)

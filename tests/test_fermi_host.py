@@ -257,7 +257,7 @@ def resources():
 
 def _row(resources, name):
     matches = [row for key, row in resources.items() if key.startswith(f"void bdg::{name}(")]
-    assert len(matches) == 1, (name, [k for k in resources if "clenshaw" in k][:8])
+    assert len(matches) == 1, (name, [k for k in resources if "FermiTail" in k or "clenshaw" in k][:8])
     return matches[0]
 
 
@@ -272,7 +272,7 @@ def test_clenshaw_kernels_do_not_spill_and_keep_their_occupancy(resources):
                 row = _row(resources, f"cheb_clenshaw_dict<bdg::{mode}, {rl}, {maxb}>")
                 assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, maxb, row)
         for rl in (4, 8, 16, 32, 64):
-            row = _row(resources, f"cheb_clenshaw<bdg::{mode}, {rl}>")
+            row = _row(resources, f"cheb_family<bdg::{mode}, {rl}, bdg::FermiTail>")
             assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, row)
     for per_lane in (1, 2):
         row = _row(resources, f"fermi_extract<{per_lane}>")

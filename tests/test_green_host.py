@@ -201,10 +201,10 @@ def test_green_kernels_do_not_spill_and_keep_their_occupancy(resources):
         lanes = (4, 8, 16, 32) if mode.startswith("Real") else (4, 8, 16, 32, 64)
         for rl in lanes:
             for maxb in (3, 5, 7):
-                row = _row(resources, f"cheb_green_dict<bdg::{mode}, {rl}, {maxb}>")
+                row = _row(resources, f"cheb_family_dict<bdg::{mode}, {rl}, {maxb}, bdg::GreenTail>")
                 assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, maxb, row)
         for rl in (4, 8, 16, 32, 64):
-            row = _row(resources, f"cheb_green<bdg::{mode}, {rl}>")
+            row = _row(resources, f"cheb_family<bdg::{mode}, {rl}, bdg::GreenTail>")
             assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, row)
     for per_lane in (1, 2):
         row = _row(resources, f"green_pick<{per_lane}>")

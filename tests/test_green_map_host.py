@@ -260,10 +260,10 @@ def test_green_local_kernels_do_not_spill_and_keep_their_occupancy(resources):
         lanes = (4, 8, 16, 32) if mode.startswith("Real") else (4, 8, 16, 32, 64)
         for rl in lanes:
             for maxb in (3, 5, 7):
-                row = _row(resources, f"cheb_green_local_dict<bdg::{mode}, {rl}, {maxb}>")
+                row = _row(resources, f"cheb_family_dict<bdg::{mode}, {rl}, {maxb}, bdg::GreenLocalTail>")
                 assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, maxb, row)
         for rl in (4, 8, 16, 32, 64):
-            row = _row(resources, f"cheb_green_local<bdg::{mode}, {rl}>")
+            row = _row(resources, f"cheb_family<bdg::{mode}, {rl}, bdg::GreenLocalTail>")
             assert row["scratch"] == 0 and row["vgpr"] <= 128 and row["occupancy"] >= 4, (mode, rl, row)
     for per_lane in (1, 2):
         row = _row(resources, f"green_local_pick<{per_lane}>")

@@ -275,9 +275,9 @@ def resources():
 def expected_instances():
     names = []
     for mode in ("RealPHMode", "ComplexPHMode", "RealMode", "ComplexMode"):
-        names += [f"cheb_green_state<bdg::{mode}, {rl}>" for rl in (4, 8, 16, 32, 64)]
+        names += [f"cheb_family<bdg::{mode}, {rl}, bdg::GreenStateTail>" for rl in (4, 8, 16, 32, 64)]
         lanes = (4, 8, 16, 32) if mode.startswith("Real") else (4, 8, 16, 32, 64)
-        names += [f"cheb_green_state_dict<bdg::{mode}, {rl}, {maxb}>" for rl in lanes for maxb in (3, 5, 7)]
+        names += [f"cheb_family_dict<bdg::{mode}, {rl}, {maxb}, bdg::GreenStateTail>" for rl in lanes for maxb in (3, 5, 7)]
     return names
 
 
@@ -287,12 +287,12 @@ def test_green_state_kernels_do_not_spill_and_keep_their_occupancy(resources):
     streamed-block form spilled 20 - 68 bytes per lane in every mode and the dictionary form 20 - 36 bytes in
     ComplexPHMode).  As built: no scratch anywhere and 4 waves per SIMD, the register class of the picked kernels; the
     dictionary form needs at most 120 VGPRs, the streamed-block form at most 120 and 128 in ComplexPHMode."""
-    emitted = sorted(re.match(r"void bdg::(cheb_green_state.*)\(bdg::GreenStateArgs\)", key).group(1)
-                     for key in resources if key.startswith("void bdg::cheb_green_state"))
+    emitted = sorted(re.match(r"void bdg::(cheb_family.*)\(bdg::GreenStateTail::Args\)", key).group(1)
+                     for key in resources if key.startswith("void bdg::cheb_family") and "bdg::GreenStateTail>" in key)
     assert emitted == sorted(expected_instances())
     for name in emitted:
-        row = resources[f"void bdg::{name}(bdg::GreenStateArgs)"]
-        limit = 128 if name.startswith("cheb_green_state<bdg::ComplexPHMode") else 120
+        row = resources[f"void bdg::{name}(bdg::GreenStateTail::Args)"]
+        limit = 128 if name.startswith("cheb_family<bdg::ComplexPHMode") else 120
         assert row["scratch"] == 0 and row["vgpr"] <= limit and row["occupancy"] >= 4, (name, row)
     helpers = [key for key in resources if re.search(r"bdg::green_state_(start|reduce|project)", key)]
     assert len(helpers) == 7  # start, reduce, project<4 .. 64>

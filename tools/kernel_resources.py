@@ -6,6 +6,7 @@
 Used by tests/test_kernel_resources.py as a regression guard: an innocent-looking edit that
 pushes a hot kernel past a VGPR step (128, 168) or makes it spill costs 10-30 %.
 """
+import functools
 import os
 import re
 import subprocess
@@ -16,6 +17,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def collect():
+    """The table, compiled once per process; every caller gets a copy of its own."""
+    return {name: dict(row) for name, row in _collect().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _collect():
     src = os.path.join(ROOT, "bodge_amd", "csrc", "bodge_hip.hip")
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
