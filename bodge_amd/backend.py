@@ -58,6 +58,9 @@ class Perf(C.Structure):
         ("green_local", C.c_int32),
         ("apply", C.c_int32),
         ("green_states", C.c_int32),
+        ("response_map", C.c_int32),
+        ("gemm_ms", C.c_double),
+        ("gemm_flops", C.c_double),
         ("correlation", C.c_int32),
         ("gram_ms", C.c_double),
         ("gram_flops", C.c_double),
@@ -106,6 +109,8 @@ SIGNATURES = {
     "bdg_apply_series": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p, _f64p]),
     "bdg_moment_matrix": (C.c_int, [_handle, C.c_double, C.c_int32, C.POINTER(Operator), C.POINTER(Operator), C.c_int32, _i64p,
                                    _f64p, _f64p]),
+    "bdg_response_map": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p, C.c_int32, _f64p, C.c_int32, _i32p,
+                                  _f64p]),
     "bdg_green_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, C.c_int32, _i32p, _f64p]),
     "bdg_green_local_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32, _f64p]),
     "bdg_green_state_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p]),

@@ -13,7 +13,7 @@
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
 //   family.hpp      the two tile loops, dispatch, launch plan and set-up shared by fermi / apply / correlation /
-//                   green / green_map / green_states.hpp
+//                   response_map / green / green_map / green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
 //   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver
@@ -65,6 +65,7 @@
 #include "fermi.hpp"
 #include "apply.hpp"
 #include "correlation.hpp"
+#include "response_map.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
 #include "green_states.hpp"
@@ -681,6 +682,12 @@ int bdg_apply_series(bdg_system* sys, double scale, int32_t n_moments, int32_t n
 int bdg_moment_matrix(bdg_system* sys, double scale, int32_t n_moments, const bdg_operator* a, const bdg_operator* b,
                       int32_t n_vectors, const int64_t* rows, const double* x, double* mu_out) {
     return run_moment_matrix(sys, scale, n_moments, a, b, n_vectors, rows, x, mu_out);
+}
+
+int bdg_response_map(bdg_system* sys, double scale, int32_t n_moments, int32_t n_source_rows, const int64_t* source_rows,
+                     const double* a, int32_t n_kernels, const double* coef, int32_t n_sites, const int32_t* block_rows,
+                     double* out) {
+    return run_response_map(sys, scale, n_moments, n_source_rows, source_rows, a, n_kernels, coef, n_sites, block_rows, out);
 }
 
 int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sources, const int64_t* source_rows,

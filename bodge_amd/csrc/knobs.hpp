@@ -70,6 +70,9 @@
 //                                            the moments are blocked (tests lower it)
 //     BODGE_AMD_CORRELATION_SLICE=entries    complex entries of a panel row per workgroup of corr_gram (default 4096, a
 //                                            multiple of 4): fixes the summation order of a moment, whatever the blocking
+//   bdg_response_map (response_map.hpp) follows the switches of bdg_moment_matrix; BODGE_AMD_CORRELATION_BYTES limits its
+//   two panels X and Z together: with fewer sites than asked for the target sites are chunked (multiples of 16 sites,
+//   every chunk reruns the recurrence; tests lower it)
 #pragma once
 
 #include <cstdlib>

@@ -577,6 +577,18 @@ class Hamiltonian:
 
         return correlation(self, A, B, **options)
 
+    def response_map(self, A, **options):
+        """The response of every site to one operator A with a support of at most 8 sites (an impurity spin, a local
+        density): a `ResponseMap` whose `blocks` (kernels, sites, 4, 4) contract with any 4×4 on-site operator,
+        `contract(B)`, `spin(k)`, `density()`: χ_AB(r) for B on every site from one recurrence on the columns of A,
+        where `correlation` answers one pair per call.  `omega=None` is the static limit at `temperature`,
+        `omega=[…]` with `broadening` the Kubo kernel, `function=F` any F(E_a, E_b).  Not part of the reference API;
+        options (temperature, broadening, omega, function, moments, sites, scale, digits) are those of
+        `bodge_amd.response_map.response_map`."""
+        from .response_map import response_map
+
+        return response_map(self, A, **options)
+
     def ldos(self, site: Coord, energies, **options) -> Matrix:
         """Local density of states at `site` for the given energies (ref :324-387)."""
         from .observables import ldos

@@ -275,6 +275,31 @@ class DeviceSolver:
             backend.as_f64p(mu.view(np.float64))))
         return mu
 
+    def response_map(self, scale, source_rows, a, coef, block_rows) -> np.ndarray:
+        """(kernels, sites, 4, 4) complex blocks K_{q,j}[γ, δ] = Σ_nm c_q[n, m] Σ_αβ A[α, β] conj(X_m[(j, γ), β])
+        X_n[(j, δ), α] with X_n = T_n(H/scale) on the unit columns of the S <= 32 distinct scalar rows `source_rows`
+        (bdg_response_map): `a` (S, S) complex between those rows, `coef` (kernels, M, M) or (M, M) complex,
+        `block_rows` the distinct target sites."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        source_rows = np.ascontiguousarray(source_rows, dtype=np.int64).reshape(-1)
+        block_rows = np.ascontiguousarray(block_rows, dtype=np.int32).reshape(-1)
+        a = np.ascontiguousarray(a, dtype=np.complex128)
+        coef = np.ascontiguousarray(coef, dtype=np.complex128)
+        if coef.ndim == 2:
+            coef = coef[None]
+        if coef.ndim != 3 or coef.shape[0] < 1 or coef.shape[1] < 1 or coef.shape[1] != coef.shape[2]:
+            raise ValueError("response_map: expected coefficients of shape (kernels, moments, moments)")
+        if source_rows.size < 1 or a.shape != (source_rows.size, source_rows.size):
+            raise ValueError("response_map: expected at least one source row and A of shape (rows, rows)")
+        if block_rows.size < 1:
+            raise ValueError("response_map: expected at least one target block row")
+        out = np.empty((coef.shape[0], block_rows.size, 4, 4), dtype=np.complex128)
+        backend.check(self._lib.bdg_response_map(
+            self._handle, float(scale), coef.shape[1], source_rows.size, backend.as_i64p(source_rows),
+            backend.as_f64p(a.view(np.float64)), coef.shape[0], backend.as_f64p(coef.view(np.float64)), block_rows.size,
+            backend.as_i32p(block_rows), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def green_moments(self, scale, n_moments, source_rows, target_block_rows) -> np.ndarray:
         """(n_moments, n_targets, 4, n_sources) complex moments <e_{4j+a}|T_n(H/scale)|e_row> for the scalar rows
         `source_rows` and the distinct block rows j of `target_block_rows` (bdg_green_moments)."""

@@ -100,6 +100,10 @@ typedef struct bdg_perf {
                               another one */
     int32_t green_states;  /* bdg_green_state_moments: 1 = its steps ran the streamed-block kernel (cheb_green_state),
                               2 = the dictionary kernel (cheb_green_state_dict); 0 = the call was another one */
+    int32_t response_map;  /* bdg_response_map: 1 = the call was this one, 0 = another one */
+    double gemm_ms;        /* bdg_response_map: HIP-event time of its product launches (resp_gemm) */
+    double gemm_flops;     /* bdg_response_map: 8 x n_moments^2 x K summed over the chunks of sites and the kernels, K = 4 x
+                              padded columns x sites of the chunk complex entries per panel row */
     int32_t correlation;   /* bdg_moment_matrix: 1 = the call was this one, 0 = another one */
     double gram_ms;        /* bdg_moment_matrix: HIP-event time of its Gram + reduce launches (corr_gram, corr_reduce) */
     double gram_flops;     /* bdg_moment_matrix: 8 x rows of X x rows of Y x K summed over the Gram launches, K = 4 nb x
@@ -253,6 +257,32 @@ typedef struct bdg_operator {
  */
 int bdg_moment_matrix(bdg_system* sys, double scale, int32_t n_moments, const bdg_operator* a, const bdg_operator* b,
                       int32_t n_vectors, const int64_t* rows, const double* x, double* mu_out);
+
+/*
+ * One operator's response at every site.  For A with support on the S = n_source_rows distinct scalar
+ * rows `source_rows` (1 <= S <= 32; a[(al*S + be)*2 + {0, 1}] = (re, im) of A between rows source_rows[al] and
+ * source_rows[be], no symmetry assumed) and n_kernels coefficient matrices coef[((q*n_moments + n)*n_moments + m)*2 +
+ * {0, 1}] = (re, im) of c_q[n][m] (as chebyshev_coefficients_2d returns them), with X_n = T_n(H/scale) E on the unit
+ * columns E of the source rows:
+ *   out[(((q*n_sites + s)*4 + g)*4 + d)*2 + {0, 1}] = (re, im) of
+ *       K_{q,j_s}[g][d] = sum_nm c_q[n][m] sum_{al,be} A[al][be] conj(X_m[4 j_s + g][be]) X_n[4 j_s + d][al]
+ * for the distinct block rows j_s = block_rows[s] in any order (the source may be among them), so that
+ * sum_{g,d} B[g][d] K[g][d] = sum_ab A_ab (B_j)_ba F_q(E_a, E_b) for any 4x4 operator B on site j: a plain trace, no
+ * factor 1/2.  The columns run through the stored-source kernels of bdg_apply_series with a zero coefficient, padded
+ * with zero columns to whole batches of the width rule (bdg_set_lanes_per_row fixes the lanes); after every step
+ * resp_pick gathers the rows of a chunk of sites into row n of a panel X (site-major), resp_gemm (fp64 MFMA) forms
+ * Z_q = c_q^T X and resp_contract sums a site's 16 entries over m and the columns: n ascending, then m ascending, no
+ * atomics - the same bits from run to run and however the sites are chunked.  X and Z hold n_moments rows each; a
+ * chunk is all sites, or the largest multiple of 16 sites for which both stay within BODGE_AMD_CORRELATION_BYTES
+ * (default 4 GiB), and every chunk reruns the recurrence; if 16 sites do not fit the call returns BDG_EINVAL with the
+ * bytes needed.  Argument errors come before any device call, in this order: counts < 1, S > 32, scale <= 0, null
+ * pointers, null handle, source rows or block rows out of range or repeated, slab.  bdg_perf_query reports the call:
+ * response_map = 1, launches = chunks x batches x (n_moments - 1), vector_steps = columns x launches, gemm_ms and
+ * gemm_flops.  Ends a Lanczos run or a subspace block on the handle.  Whole matrices only (not slabs).
+ */
+int bdg_response_map(bdg_system* sys, double scale, int32_t n_moments, int32_t n_source_rows, const int64_t* source_rows,
+                     const double* a, int32_t n_kernels, const double* coef, int32_t n_sites, const int32_t* block_rows,
+                     double* out);
 
 /*
  * Off-diagonal Chebyshev moments for the Green's function blocks G_ji:
