@@ -39,7 +39,9 @@ int eigh_jacobi_typed(bdg_system* sys, double* w_out, double* z_out) {
             if (int rc = V.reserve((size_t)n * n)) return rc;
         if (int rc = eig.reserve((size_t)n)) return rc;
         if (int rc = counter.reserve(1)) return rc;
-        const double shift = 1.5 * sys->gershgorin + 1.0;  // spectrum of G in [0.5 b + 1, 2.5 b + 1]
+        // spectrum of G in [0.5 b, 2.5 b]: proportional to the matrix, so that the eigenvalues of A = G - shift keep eps |G|
+        // = a few eps b whatever the scale of A (with a constant added, a matrix of norm 2^-40 lost eps x 1); b = 0: A = 0
+        const double shift = sys->gershgorin > 0.0 ? 1.5 * sys->gershgorin : 1.0;
         HIP_TRY(hipMemsetAsync(G.ptr, 0, sizeof(T) * n * n, st));
         scatter_for_jacobi(sys, G.ptr, st);
         bdg::jacobi_setup<T><<<(unsigned)std::min<int64_t>(4096, (n * n + 255) / 256), 256, 0, st>>>(
@@ -63,7 +65,7 @@ int eigh_jacobi_typed(bdg_system* sys, double* w_out, double* z_out) {
             if (rotations == 0) break;
         }
         if (sweep == max_sweeps) return fail(BDG_ELIBRARY, "Jacobi eigensolver did not converge in %d sweeps", max_sweeps);
-        bdg::jacobi_eigenvalues<T><<<(unsigned)n, 256, 0, st>>>(G.ptr, (int)n, shift, eig.ptr);
+        bdg::jacobi_eigenvalues<T><<<(unsigned)n, 256, 0, st>>>(G.ptr, z_out ? V.ptr : nullptr, (int)n, shift, eig.ptr);
         HIP_TRY(hipGetLastError());
         std::vector<double> vals((size_t)n);
         HIP_TRY(hipMemcpyAsync(vals.data(), eig.ptr, sizeof(double) * n, hipMemcpyDeviceToHost, st));

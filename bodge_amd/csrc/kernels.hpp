@@ -1502,15 +1502,18 @@ __global__ __launch_bounds__(256) void jacobi_round(T* __restrict__ G, T* __rest
     }
     if (threadIdx.x == 0) {
         const double aa = red[0][0], bb = red[1][0], re = red[2][0], im = red[3][0];
-        const double mag = sqrt(re * re + im * im);
+        const double mag = hypot(re, im);
         if (mag <= tol * sqrt(aa * bb) || mag == 0.0) {
             rot[1] = 0.0;
         } else {
             const double zeta = (bb - aa) / (2.0 * mag);
             const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-            const double cs = 1.0 / sqrt(1.0 + t * t);
-            rot[0] = cs;
-            rot[1] = cs * t;
+            // (cs, sn) = (1, t) / |(1, t)|, each rounded once.  cs = 1 / sqrt(1 + t t), sn = cs t left cs^2 + sn^2 - 1 with a
+            // positive mean: over the ~10 n rotations a column takes, its norm - and with it the eigenvalue |g_p| - drifted
+            // by 1 to 5 n eps; like this the deviations have no sign and add up like a random walk
+            const double h = hypot(1.0, t);
+            rot[0] = 1.0 / h;
+            rot[1] = t / h;
             rot[2] = re / mag;
             rot[3] = im / mag;
             atomicAdd(rotations, 1);
@@ -1558,21 +1561,39 @@ __global__ void jacobi_setup(T* __restrict__ G, T* __restrict__ V, int n, double
     }
 }
 
-// eig[p] = |g_p| - shift, one block per column
+// eig[p] = |g_p| / |v_p| - shift, one block per column.  v_p is the product of the rotations and g_p = G v_p: whatever the
+// rotations did to the norm of the one they did to the other, so the quotient is free of it; v_p is normalised here.
+// Without vectors (V = nullptr) |v_p| counts as 1.
+__device__ inline void jscale(double2& v, double s) { v.x *= s, v.y *= s; }
+__device__ inline void jscale(double& v, double s) { v *= s; }
+
 template <typename T>
-__global__ __launch_bounds__(256) void jacobi_eigenvalues(const T* __restrict__ G, int n, double shift,
+__global__ __launch_bounds__(256) void jacobi_eigenvalues(const T* __restrict__ G, T* __restrict__ V, int n, double shift,
                                                           double* __restrict__ eig) {
-    __shared__ double red[256];
+    __shared__ double red[2][256];
     const T* g = G + (size_t)blockIdx.x * n;
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) a += jnorm2(g[i]);
-    red[threadIdx.x] = a;
+    T* v = V ? V + (size_t)blockIdx.x * n : nullptr;
+    double a = 0.0, b = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        a += jnorm2(g[i]);
+        if (v) b += jnorm2(v[i]);
+    }
+    red[0][threadIdx.x] = a;
+    red[1][threadIdx.x] = b;
     __syncthreads();
     for (int stride = 128; stride > 0; stride >>= 1) {
-        if ((int)threadIdx.x < stride) red[threadIdx.x] += red[threadIdx.x + stride];
+        if ((int)threadIdx.x < stride) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + stride];
+            red[1][threadIdx.x] += red[1][threadIdx.x + stride];
+        }
         __syncthreads();
     }
-    if (threadIdx.x == 0) eig[blockIdx.x] = sqrt(red[0]) - shift;
+    const double v2 = v && red[1][0] > 0.0 ? red[1][0] : 1.0;
+    if (threadIdx.x == 0) eig[blockIdx.x] = sqrt(red[0][0] / v2) - shift;
+    if (v) {
+        const double scale = 1.0 / sqrt(v2);
+        for (int i = threadIdx.x; i < n; i += 256) jscale(v[i], scale);
+    }
 }
 
 // max |H - H^†| over the stored entries (reference hamiltonian.py:121-122, `M - M.getH()`): block

@@ -441,7 +441,7 @@ __global__ __launch_bounds__(64) void td_bisect(const double* __restrict__ d, co
 
 // ---- eigenvectors of the tridiagonal matrix by inverse iteration (the scheme of LAPACK's dstein).
 // One wave per cluster of close eigenvalues; its members are treated one after the other: LU of T - λ
-// with partial pivoting (lane 0; scratch in global memory), three solves from a pseudo-random start,
+// with partial pivoting (scratch in global memory), five solves from a pseudo-random start,
 // each followed by an orthogonalisation against the members already done and a normalisation (all
 // lanes).  Singletons - almost every eigenvalue - need no orthogonalisation: eigenvalues further apart
 // than the cluster tolerance give vectors orthogonal to ε|T| / gap.  Output z[i * ld + (k - first_index)].
@@ -469,10 +469,13 @@ __device__ inline double td_from_lane(double v, int src) {  // src wave-uniform
 // iterations decorrelate).  No orthogonalisation here: clusters are orthonormalised afterwards by
 // td_cluster_orthonormalise - the members of a degenerate level (50 of them on a 50 x 50 lattice) need not
 // wait for each other.
+// `members` (or nullptr: all n_vec columns) lists the columns to work on; `from_z`: start from the column as it stands
+// instead of a pseudo-random vector (the refinement of cluster members after their orthonormalisation).
 __global__ __launch_bounds__(64) void td_inverse_iteration(const double* __restrict__ d, const double* __restrict__ e,
                                                            int n, const double* __restrict__ shift, int n_vec,
                                                            double norm_t, double* __restrict__ scratch,
-                                                           double* __restrict__ z, int ld) {
+                                                           double* __restrict__ z, int ld, const int* __restrict__ members,
+                                                           int iterations, bool from_z) {
     const int lane = threadIdx.x;
     double* lu_a = scratch + (size_t)blockIdx.x * 6 * n;  // pivots
     double* lu_b = lu_a + n;                              // first super-diagonal of U
@@ -483,14 +486,17 @@ __global__ __launch_bounds__(64) void td_inverse_iteration(const double* __restr
     const double eps = 2.220446049250313e-16;
     const double tiny = eps * norm_t;
     {
-        for (int k_eig = blockIdx.x; k_eig < n_vec; k_eig += gridDim.x) {
+        for (int idx = blockIdx.x; idx < n_vec; idx += gridDim.x) {
+            const int k_eig = members ? members[idx] : idx;
             const double lambda = shift[k_eig];
-            // ---- LU factorisation of T - lambda with partial pivoting (LAPACK dlagtf): a = pivots, b / d = first and
+            // ---- LU factorisation of T - lambda with partial pivoting (the layout of LAPACK's dlagtf): a = pivots, b / d = first and
             // second super-diagonal of U, c = multipliers, in = 1 where rows k, k+1 were interchanged
             {
                 double a_k = d[0] - lambda;           // pivot candidate of the current row
                 double b_k = n > 1 ? e[0] : 0.0;      // its super-diagonal entry (changed by an interchange above it)
-                double scale1 = fabs(a_k) + fabs(b_k);
+                // Plain partial pivoting: multipliers of at most 1.  dlagtf's row-scaled comparison lets them grow without
+                // bound; in a degenerate level of a T that splits (pivots of k x nudge, couplings of rounding size) that put
+                // 1e-13 of other levels into the vectors, five solves or not.
                 for (int t = 0; t < n; t += kWave) {
                     const int row = t + lane;
                     const double sub_l = row < n - 1 ? e[row] : 0.0;                    // c(row): sub-diagonal below row
@@ -503,14 +509,10 @@ __global__ __launch_bounds__(64) void td_inverse_iteration(const double* __restr
                         double oa = a_k, ob = b_k, oc = 0.0, od = 0.0, oin = 0.0;
                         if (k < n - 1) {
                             const double sub = td_from_lane(sub_l, i), a1 = td_from_lane(a1_l, i), b1 = td_from_lane(b1_l, i);
-                            const double scale2 = fabs(sub) + fabs(a1) + fabs(b1);
-                            const double piv1 = a_k == 0.0 ? 0.0 : fabs(a_k) / scale1;
                             if (sub == 0.0) {
-                                scale1 = scale2;
                                 a_k = a1;
                                 b_k = b1;
-                            } else if (fabs(sub) / scale2 <= piv1) {  // no interchange
-                                scale1 = scale2;
+                            } else if (fabs(sub) <= fabs(a_k)) {  // no interchange
                                 oc = sub / a_k;
                                 a_k = a1 - oc * b_k;
                                 b_k = b1;
@@ -529,14 +531,14 @@ __global__ __launch_bounds__(64) void td_inverse_iteration(const double* __restr
                     if (row < n) lu_a[row] = out_a, lu_b[row] = out_b, lu_c[row] = out_c, lu_d[row] = out_d, lu_in[row] = out_in;
                 }
             }
-            for (int i = lane; i < n; i += kWave) {  // pseudo-random start in (-1, 1)
+            for (int i = lane; i < n; i += kWave) {  // pseudo-random start in (-1, 1), or the column itself
                 const uint64_t h = splitmix64(((uint64_t)(k_eig + 1) << 32) ^ (uint64_t)i);
-                x[i] = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+                x[i] = from_z ? z[(size_t)i * ld + k_eig] : (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
             }
             __syncthreads();
             // (five solves, dstein's MAXITS: three left one vector in ~250 random periodic lattices with 1e-7 of a level
             // 4e-5 |T| away - residual 4e-11, overlap 4e-8; scratch/r3_cluster_diag.py)
-            for (int iteration = 0; iteration < 5; ++iteration) {
+            for (int iteration = 0; iteration < iterations; ++iteration) {
                 double norm2 = 0.0;
                 for (int i = lane; i < n; i += kWave) norm2 += x[i] * x[i];
                 norm2 = td_wave_sum(norm2);
@@ -1084,6 +1086,7 @@ int eig_tridiagonal_typed(bdg_system* sys, double* w_out, double lower_bound, in
     DeviceBuffer<double> diag;                    // d, e, e^2, eigenvalues (n each)
     DeviceBuffer<double> zt, scratch;             // tridiagonal eigenvectors, LU work space
     DeviceBuffer<bdg::TdCluster> clusters_dev;
+    DeviceBuffer<int> members_dev;
     DeviceBuffer<double2> emitted;
     DeviceBuffer<bdg::TdScalars<T>> scal;
     TsKeep keep;
@@ -1193,6 +1196,8 @@ int eig_tridiagonal_typed(bdg_system* sys, double* w_out, double lower_bound, in
         // clusters: runs of eigenvalues closer than 1e-5 |T| are orthogonalised against each other afterwards; everything
         // further apart is orthogonal to eps |T| / gap <= 2e-11 from inverse iteration alone.  Column m of zt = eigenvalue first + m.
         const double cluster_gap = 1e-5 * std::max(span, 1e-300), nudge = 10.0 * 2.220446049250313e-16 * span;
+        // the pivot floor of the inverse iterations is eps times this: for the zero matrix (span = 0) a floor of 0 divided 0 by 0
+        const double pivot_norm = span > 0.0 ? span : 1.0;
         std::vector<bdg::TdCluster> clusters;  // (first = column, count >= 2)
         std::vector<double> shift((size_t)n_vec);
         for (int64_t k = first, run = 0; k < n; ++k) {
@@ -1220,7 +1225,7 @@ int eig_tridiagonal_typed(bdg_system* sys, double* w_out, double lower_bound, in
                 va.n = (int)n;
                 va.shift = shift_dev;
                 va.n_vec = (int)n_vec;
-                va.norm = span;
+                va.norm = pivot_norm;
                 va.scratch = scratch.ptr;
                 va.z = zt.ptr;
                 va.ld = (int)n_vec;
@@ -1233,12 +1238,30 @@ int eig_tridiagonal_typed(bdg_system* sys, double* w_out, double lower_bound, in
             if (int rc = scratch.reserve((size_t)n_waves * 6 * n + (size_t)n_vec)) return rc;
             double* shift_dev = scratch.ptr + (size_t)n_waves * 6 * n;
             HIP_TRY(hipMemcpyAsync(shift_dev, shift.data(), sizeof(double) * n_vec, hipMemcpyHostToDevice, st));
-            bdg::td_inverse_iteration<<<n_waves, 64, 0, st>>>(d, e, (int)n, shift_dev, (int)n_vec, span, scratch.ptr, zt.ptr, (int)n_vec);
+            bdg::td_inverse_iteration<<<n_waves, 64, 0, st>>>(d, e, (int)n, shift_dev, (int)n_vec, pivot_norm, scratch.ptr, zt.ptr, (int)n_vec,
+                                                              nullptr, 5, false);
         }
+        std::vector<int> members;  // columns that belong to a cluster
         if (!clusters.empty()) {
             if (int rc = clusters_dev.reserve(clusters.size())) return rc;
             HIP_TRY(hipMemcpyAsync(clusters_dev.ptr, clusters.data(), sizeof(bdg::TdCluster) * clusters.size(), hipMemcpyHostToDevice, st));
             bdg::td_cluster_orthonormalise<<<(unsigned)clusters.size(), 256, 0, st>>>(clusters_dev.ptr, (int)n, zt.ptr, (int)n_vec);
+            if (!two_stage) {
+                // The members were iterated independently of each other, so in a many-fold level the last ones can lie in
+                // the span of the others down to 1e-3 and less (the smallest singular value of k random directions), and the
+                // orthonormalisation then magnifies what they hold of OTHER levels by as much.  One more solve from the
+                // orthonormal basis removes that (other levels shrink by nudge / gap), and as the basis is orthonormal and
+                // the solve nearly isotropic inside the level, the second orthonormalisation finds remainders near 1.
+                for (const bdg::TdCluster& c : clusters)
+                    for (int m = 0; m < c.count; ++m) members.push_back(c.first + m);
+                if (int rc = members_dev.reserve(members.size())) return rc;
+                HIP_TRY(hipMemcpyAsync(members_dev.ptr, members.data(), sizeof(int) * members.size(), hipMemcpyHostToDevice, st));
+                const int refine_waves = (int)std::min<size_t>(members.size(), 7168);
+                bdg::td_inverse_iteration<<<refine_waves, 64, 0, st>>>(d, e, (int)n, scratch.ptr + (size_t)std::min<int64_t>(n_vec, 7168) * 6 * n,
+                                                                     (int)members.size(), pivot_norm, scratch.ptr, zt.ptr, (int)n_vec,
+                                                                     members_dev.ptr, 1, true);
+                bdg::td_cluster_orthonormalise<<<(unsigned)clusters.size(), 256, 0, st>>>(clusters_dev.ptr, (int)n, zt.ptr, (int)n_vec);
+            }
         }
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));  // (the host lists leave scope; errors of the kernels surface here)
@@ -1341,6 +1364,7 @@ int eig_tridiagonal_typed(bdg_system* sys, double* w_out, double lower_bound, in
     zt.release();
     scratch.release();
     clusters_dev.release();
+    members_dev.release();
     emitted.release();
     scal.release();
     return rc;
