@@ -36,14 +36,14 @@ from .common import (
 )
 from .correlation import MomentMatrix
 from .fermi import FermiMatrix
-from .green import GreenFunction, GreenMap, GreenStates
+from .green import GreenBonds, GreenFunction, GreenMap, GreenStates
 from .hamiltonian import Hamiltonian, dwave, pwave, ssd, swave
 from .lattice import CubicLattice, Lattice
 from .response_map import ResponseMap
 
 __version__ = "0.1.0"
 __all__ = [
-    "Lattice", "CubicLattice", "Hamiltonian", "FermiMatrix", "GreenFunction", "GreenMap", "GreenStates", "MomentMatrix", "ResponseMap", "Coord", "Coords", "Index", "Indices",
+    "Lattice", "CubicLattice", "Hamiltonian", "FermiMatrix", "GreenBonds", "GreenFunction", "GreenMap", "GreenStates", "MomentMatrix", "ResponseMap", "Coord", "Coords", "Index", "Indices",
     "ssd", "swave", "pwave", "dwave",
     "π", "σ", "σ0", "σ1", "σ2", "σ3", "jσ", "jσ0", "jσ1", "jσ2", "jσ3",
     "pi", "sigma", "sigma0", "sigma1", "sigma2", "sigma3",

@@ -58,6 +58,7 @@ class Perf(C.Structure):
         ("green_local", C.c_int32),
         ("apply", C.c_int32),
         ("green_states", C.c_int32),
+        ("green_bonds", C.c_int32),
         ("response_map", C.c_int32),
         ("gemm_ms", C.c_double),
         ("gemm_flops", C.c_double),
@@ -113,6 +114,7 @@ SIGNATURES = {
                                   _f64p]),
     "bdg_green_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, C.c_int32, _i32p, _f64p]),
     "bdg_green_local_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32, _f64p]),
+    "bdg_green_bond_blocks": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, _i32p, _i32p, C.c_int32, _f64p]),
     "bdg_green_state_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p]),
     "bdg_cheb_diag_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p]),
     "bdg_lanczos_begin": (C.c_int, [_handle, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),

@@ -13,7 +13,7 @@
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
 //   family.hpp      the two tile loops, dispatch, launch plan and set-up shared by fermi / apply / correlation /
-//                   response_map / green / green_map / green_states.hpp
+//                   response_map / green / green_map / green_bonds / green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
 //   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver
@@ -68,6 +68,7 @@
 #include "response_map.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
+#include "green_bonds.hpp"
 #include "green_states.hpp"
 #include "lanczos.hpp"
 #include "subspace.hpp"
@@ -698,6 +699,11 @@ int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t 
 int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
                             const int32_t* block_rows, int32_t n_components, double* out) {
     return run_green_local_moments(sys, scale, n_moments, n_sites, block_rows, n_components, out);
+}
+
+int bdg_green_bond_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
+                          const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* out) {
+    return run_green_bond_blocks(sys, scale, n_moments, n_weights, weights, pat_indptr, pat_indices, n_components, out);
 }
 
 int bdg_green_state_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_states,

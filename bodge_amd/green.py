@@ -1,4 +1,5 @@
-"""Local and non-local blocks of the retarded Green's function (`Hamiltonian.green`, `Hamiltonian.green_map`).
+"""Local and non-local blocks of the retarded Green's function (`Hamiltonian.green`, `Hamiltonian.green_map`,
+`Hamiltonian.green_bonds`).
 
 G(z) = (z - H)^-1 at z = ε + iΓ for the whole 4N x 4N BdG matrix, Nambu basis (e↑, e↓, h↑, h↓) per site.
 `GreenFunction.blocks[t, k]` = G(E_k + iΓ_k)[4j_t:4j_t+4, 4i:4i+4] for the source site i and the target
@@ -19,6 +20,12 @@ Maps: `green_map` wants the local block G_jj at many sites j.  
 sites share one batch of the recurrence, and a step stores for every vector the rows of its own site only
 (`bdg_green_local_moments`), so a launch runs at full width and the moment table grows with the number of
 sites, not with its square.
+
+Bonds: `green_bonds` wants G_ji on every block (j, i) of H's skeleton whose column i is one of the
+source sites - the bond anomalous function of a d- or p-wave superconductor, the spectral current.  The batches are
+those of `green_map`; a step stores, on every block row j, the entries of the vectors that started on a site i with
+(j, i) in the pattern, and the moments are contracted with the series weights on the device
+(`bdg_green_bond_blocks`): only energies x blocks x 16 numbers come back.
 
 Extended states: `green_states` wants <w a|G|w b> for a state w spread over the lattice, with
 |w b> = Σ_j w[j] e_{4j+b} - G(k, ε) for a plane wave (`spectral_function`).  The Nambu vectors of up to 64 / C
@@ -250,6 +257,150 @@ def green_map(system, energies, sites=None, *, broadening=None, moments: int | N
     info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
             "perf": perf[0] if len(perf) == 1 else perf}
     return GreenMap(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, sites, info)
+
+
+class GreenBonds:
+    """Blocks of G(ε + iΓ) on a pattern of site pairs: the skeleton blocks (j, i) of H whose column i is a source site.
+
+    `blocks` (nnz, K, 4, 4) complex128: blocks[k, e] = G(E_e + iΓ_e)[4j:4j+4, 4i:4i+4] for block k = (block row j,
+    block column i); `indptr` / `indices` the pattern (int32, BSR, as in `FermiMatrix`), `energies` and `broadening`
+    (K,), `lattice` the system's, `info` the route details as in `GreenFunction`.  The helpers are slices and sums of
+    the blocks, so no sign convention is hidden in them.
+    """
+
+    def __init__(self, lattice, indptr: np.ndarray, indices: np.ndarray, blocks: np.ndarray, energies: np.ndarray,
+                 broadening: np.ndarray, info: dict | None = None, skeleton=None):
+        self.lattice = lattice
+        self.indptr = indptr
+        self.indices = indices
+        self.blocks = blocks
+        self.energies = energies
+        self.broadening = broadening
+        self.info = dict(info or {})
+        n = lattice.size
+        self._rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr))
+        self._keys = self._rows * n + indices
+        self._mirror = None
+        self._skeleton = skeleton  # (blocks of the system's skeleton, index of every pattern block in it) or None
+
+    def _find(self, rows: np.ndarray, cols: np.ndarray) -> np.ndarray:
+        wanted = rows * self.lattice.size + cols
+        found = np.minimum(np.searchsorted(self._keys, wanted), len(self._keys) - 1)
+        if np.any(self._keys[found] != wanted):
+            raise IndexError("The pattern has no block for this pair of sites")
+        return found
+
+    def block(self, j: Coord, i: Coord) -> np.ndarray:
+        """(K, 4, 4) G[4j:4j+4, 4i:4i+4] for lattice coordinates j (row, target) and i (column, source); a copy."""
+        k = self._find(np.array([self.lattice[j]], dtype=np.int64), np.array([self.lattice[i]], dtype=np.int64))[0]
+        return self.blocks[k].copy()
+
+    def local(self) -> GreenMap:
+        """The diagonal blocks G_ii of the source sites as a `GreenMap` (ldos(), spin_ldos(), ...), in index order."""
+        diagonal = np.flatnonzero(self._rows == self.indices)
+        coords = list(self.lattice.sites())
+        sites = [coords[int(i)] for i in self.indices[diagonal]]
+        return GreenMap(np.ascontiguousarray(self.blocks[diagonal]), self.energies, self.broadening, sites, self.info)
+
+    def anomalous(self, j: Coord, i: Coord) -> np.ndarray:
+        """(K, 2, 2) the electron-hole block G_ji[0:2, 2:4]: the pair function on the bond (j, i)."""
+        return self.block(j, i)[:, 0:2, 2:4]
+
+    def _mirrors(self) -> np.ndarray:
+        if self._mirror is None:
+            self._mirror = self._find(self.indices.astype(np.int64), self._rows)
+        return self._mirror
+
+    def spectral(self) -> np.ndarray:
+        """(nnz, K, 4, 4) A_ji(ε) = (i/2π)(G_ji - conj(G_ij)ᵀ): the blocks of (i/2π)(G - G†), a broadened δ(ε - H).
+        Needs the mirror block (i, j) of every block (j, i): IndexError where the pattern lacks one."""
+        mirror = self.blocks[self._mirrors()]
+        return (0.5j / np.pi) * (self.blocks - mirror.conj().transpose(0, 1, 3, 2))
+
+    def _operator_blocks(self, dH) -> np.ndarray:
+        """(nnz, 4, 4) blocks of dH on this pattern: a block array on the pattern, a Hamiltonian on the same lattice
+        (its blocks), a block array on the system's skeleton, or a sparse (4N, 4N) matrix without entries elsewhere."""
+        import scipy.sparse as sp
+
+        if sp.issparse(dH):
+            coo = sp.coo_matrix(dH)
+            n = self.lattice.size
+            if coo.shape != (4 * n, 4 * n):
+                raise ValueError(f"expected an operator of shape {(4 * n, 4 * n)}, got {coo.shape}")
+            keep = coo.data != 0
+            row, col, values = coo.row[keep].astype(np.int64), coo.col[keep].astype(np.int64), coo.data[keep]
+            try:
+                where = self._find(row // 4, col // 4) if row.size else np.zeros(0, dtype=np.int64)
+            except IndexError:
+                raise ValueError("the operator has entries outside the pattern of these blocks") from None
+            data = np.zeros(self.blocks.shape[:1] + (4, 4), dtype=np.complex128)
+            np.add.at(data, (where, row % 4, col % 4), values)
+            return data
+        data = np.asarray(getattr(dH, "_data", dH))
+        wanted = self.blocks.shape[:1] + (4, 4)
+        if data.shape != wanted and self._skeleton is not None and data.shape == (self._skeleton[0], 4, 4):
+            data = data[self._skeleton[1]]
+        if data.shape != wanted:
+            raise ValueError(f"expected blocks of shape {wanted} on the same pattern, got {data.shape}")
+        return data
+
+    def expectation(self, dH) -> np.ndarray:
+        """(K,) complex ½ Σ_{(i,j) in pattern} tr(A_ji(ε) dH_ij) with A = spectral(), the conventions of
+        `FermiMatrix.expectation`: ∫ f(ε)·expectation(dH) dε tends to `FermiMatrix.expectation(dH)` as Γ -> 0.  With
+        dH = `correlation.current_operator(system, axis)` it is the spectral current; real up to round-off for
+        Hermitian dH."""
+        data = self._operator_blocks(dH)
+        return 0.5 * np.einsum("keab,kba->e", self.spectral()[self._mirrors()], data)
+
+
+def green_bonds(system, energies, sites=None, *, broadening=None, moments: int | None = None, digits: float = 12.0,
+                scale: float | None = None, _all_columns: bool = False) -> GreenBonds:
+    """G_ji(E + iΓ) on every skeleton block (j, i) of H with i among `sites` (see `Hamiltonian.green_bonds`)."""
+    n = system.lattice.size
+    if sites is None:
+        columns_wanted = np.arange(n, dtype=np.int64)
+    else:
+        columns_wanted = np.array([system.lattice[tuple(site)] for site in sites], dtype=np.int64)
+    if columns_wanted.size == 0:
+        raise ValueError("green: sites is empty")
+    energies, gamma, moments, scale = _series_arguments(system, energies, broadening, moments, digits, scale)
+
+    full_indptr = np.asarray(system._matrix.indptr, dtype=np.int64)
+    full_indices = np.asarray(system._matrix.indices, dtype=np.int64)
+    full_rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(full_indptr))
+    distinct = np.unique(columns_wanted)  # (a site is a source once, whatever the order of the list)
+    wanted = np.zeros(n, dtype=bool)
+    wanted[distinct] = True
+    kept = np.flatnonzero(wanted[full_indices])  # the pattern: skeleton blocks with a source site for a column
+    rows, cols = full_rows[kept], full_indices[kept]
+    indptr = np.zeros(n + 1, dtype=np.int32)
+    np.cumsum(np.bincount(rows, minlength=n), out=indptr[1:])
+    indices = cols.astype(np.int32)
+
+    derive = not _all_columns and system.has_symmetric_spectrum(1e-12)
+    columns = 2 if derive else 4
+    solver = system._solver()
+    weights = moment_weights(moments, scale, energies + 1j * gamma)
+    # groups of source sites whose result (energies x blocks x 256 B) stays within the host limit
+    per_site = np.bincount(cols, minlength=n)[distinct] * energies.size * 256
+    blocks = np.empty((kept.size, energies.size, 4, 4), dtype=np.complex128)
+    perf, lo = [], 0
+    while lo < distinct.size:
+        hi = lo + max(1, int(np.searchsorted(np.cumsum(per_site[lo:]), HOST_TABLE_LIMIT, side="right")))
+        if hi < distinct.size and hi - lo > 64:
+            hi -= (hi - lo) % 64  # (whole device batches)
+        member = np.zeros(n, dtype=bool)
+        member[distinct[lo:hi]] = True
+        part = np.flatnonzero(member[cols])
+        part_indptr = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum(np.bincount(rows[part], minlength=n), out=part_indptr[1:])
+        result = solver.green_bond_blocks(scale, weights, part_indptr, indices[part], columns)
+        perf.append(solver.perf())
+        blocks[part] = result.transpose(1, 0, 2, 3)
+        lo = hi
+    info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+            "perf": perf[0] if len(perf) == 1 else perf}
+    return GreenBonds(system.lattice, indptr, indices, blocks, energies, gamma, info, (full_indices.size, kept))
 
 
 class GreenStates:

@@ -529,6 +529,17 @@ class Hamiltonian:
 
         return green_map(self, energies, sites, **options)
 
+    def green_bonds(self, energies, sites=None, **options):
+        """Blocks G_ji(ε + iΓ) of the retarded Green's function on every block (j, i) of this Hamiltonian's skeleton
+        (the site itself, every bond and periodic-edge pair) whose column i is one of the source sites `sites`
+        (default: every site), as a `GreenBonds` with block(j, i), local() (a `GreenMap`), anomalous(j, i), spectral()
+        and expectation(dH): the bond pair function of d- and p-wave superconductors, the spectral current.  The
+        moments are contracted to energies on the GPU.  Not part of the reference API; options (broadening, moments,
+        digits, scale) are those of `green`."""
+        from .green import green_bonds
+
+        return green_bonds(self, energies, sites, **options)
+
     def green_states(self, states, energies, **options):
         """Blocks <w a|G(ε + iΓ)|w b> of the retarded Green's function between the four Nambu vectors of extended
         states: `states` (Q, N) or (N,) holds one complex amplitude per site in site-index order (plane waves, wave

@@ -327,6 +327,27 @@ class DeviceSolver:
             int(n_components), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def green_bond_blocks(self, scale, weights, indptr, indices, n_components: int = 4) -> np.ndarray:
+        """(n_weights, nnz, 4, 4) complex Σ_n weights[e, n] <e_{4j+a}|T_n(H/scale)|e_{4i+b}> on the blocks k = (j, i) of
+        the BSR pattern (`indptr`, `indices`), every column site a source; the moments are contracted on the device
+        (bdg_green_bond_blocks).  `weights` (n_weights, n_moments) complex; n_components = 2 derives the hole columns
+        from the electron columns (particle-hole symmetric matrices only)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        weights = np.ascontiguousarray(weights, dtype=np.complex128)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int32).reshape(-1)
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        if weights.ndim != 2 or weights.shape[0] < 1 or weights.shape[1] < 1:
+            raise ValueError("green_bond_blocks: expected weights of shape (energies, moments)")
+        if indptr.shape != (self.n_sites + 1,) or indices.size < 1 or int(indptr[-1]) != indices.size:
+            raise ValueError(f"green_bond_blocks: the pattern does not describe the handle's {self.n_sites} block rows")
+        if int(n_components) not in (2, 4):
+            raise ValueError("green_bond_blocks: expected 2 or 4 components")
+        out = np.empty((weights.shape[0], indices.size, 4, 4), dtype=np.complex128)
+        backend.check(self._lib.bdg_green_bond_blocks(
+            self._handle, float(scale), weights.shape[1], weights.shape[0], backend.as_f64p(weights.view(np.float64)),
+            backend.as_i32p(indptr), backend.as_i32p(indices), int(n_components), backend.as_f64p(out.view(np.float64))))
+        return out
+
     def green_state_moments(self, scale, n_moments, amplitudes, n_components: int = 4) -> np.ndarray:
         """(n_moments, n_states, 4, n_components) complex moments <w_q a|T_n(H/scale)|w_q b> of the states
         `amplitudes` (n_states, n_sites): one complex amplitude per site, the same on every Nambu component

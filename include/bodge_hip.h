@@ -92,7 +92,7 @@ typedef struct bdg_perf {
     int32_t green;         /* bdg_green_moments: 1 = its picked steps ran the streamed-block kernel (cheb_green),
                               2 = the dictionary kernel (cheb_green_dict); 0 = the call was another one */
     int32_t green_ranges;  /* bdg_green_moments, bdg_green_local_moments, bdg_green_state_moments: ranges of moments the
-                              device table was filled and copied out in */
+                              device table was filled and copied out in (bdg_green_bond_blocks: filled and contracted in) */
     int32_t green_local;   /* bdg_green_local_moments: 1 = its steps ran the streamed-block kernel (cheb_green_local),
                               2 = the dictionary kernel (cheb_green_local_dict); 0 = the call was another one */
     int32_t apply;         /* bdg_apply_series: 1 = its stored-source Clenshaw steps ran the streamed-block kernel
@@ -100,6 +100,8 @@ typedef struct bdg_perf {
                               another one */
     int32_t green_states;  /* bdg_green_state_moments: 1 = its steps ran the streamed-block kernel (cheb_green_state),
                               2 = the dictionary kernel (cheb_green_state_dict); 0 = the call was another one */
+    int32_t green_bonds;   /* bdg_green_bond_blocks: 1 = its steps ran the streamed-block kernel, 2 = the dictionary kernel
+                              (cheb_family / cheb_family_dict with GreenBondTail); 0 = the call was another one */
     int32_t response_map;  /* bdg_response_map: 1 = the call was this one, 0 = another one */
     double gemm_ms;        /* bdg_response_map: HIP-event time of its product launches (resp_gemm) */
     double gemm_flops;     /* bdg_response_map: 8 x n_moments^2 x K summed over the chunks of sites and the kernels, K = 4 x
@@ -312,6 +314,32 @@ int bdg_green_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t 
  */
 int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_sites,
                             const int32_t* block_rows, int32_t n_components, double* out);
+
+/*
+ * Green's function blocks on a pattern of block pairs, every column site a source:
+ *   out[(((e*nnz + k)*4 + a)*4 + b)*2 + {0, 1}] = (re, im) of sum_n w[e][n] <e_{4j + a}|T_n(H/scale)|e_{4i + b}>
+ * for e < n_weights, the pattern block k = (block row j, column pat_indices[k]) with i = pat_indices[k], nnz =
+ * pat_indptr[nb], a, b < 4, and the weights weights[(e*n_moments + n)*2 + {0, 1}] = (re, im) of w[e][n] (for G(z_e):
+ * the series weights of the resolvent).  The pattern is a BSR skeleton as in bdg_fermi_blocks, any subset of block
+ * pairs in canonical order (columns ascending within a row, no duplicates); the column sites of the call are the
+ * distinct entries of pat_indices.  The unit vectors of up to 64 / n_components column sites share one batch of the
+ * one-step width rule (bdg_set_lanes_per_row fixes the lanes), n_components = 2 (the electron columns; the hole
+ * columns follow from mu_n[a][b] = (-1)^n conj mu_n[a^2][b^2] on the same block, right for a particle-hole symmetric
+ * matrix only) or 4.  One launch per moment advances all vectors, and on block row j the vectors of site i store
+ * their entries of every pattern block (j, i) (kernels cheb_family / cheb_family_dict with GreenBondTail: one writer
+ * per entry).  The moments stay on the device: the table covers a range of moments of at most 256 MB
+ * (BODGE_AMD_GREEN_TABLE_BYTES), and when it is full green_bond_contract adds the range to the result in ascending n,
+ * one chain of FMAs per entry, no atomics - the same bits from run to run and however the moments are cut into
+ * ranges.  Only `out` leaves the device.  Argument errors come before any device call, in this order: counts < 1
+ * (n_moments, n_weights; n_weights above 262140), scale <= 0, null pointers, null handle, a pattern whose indptr does
+ * not start at 0 or is not monotone, that has no block, whose indices leave [0, nb) or are not in canonical order,
+ * n_components not 2 or 4, slab.  bdg_perf_query reports the call: green_bonds says which kernel form ran, launches =
+ * batches x (n_moments - 1), kernel_ms the recurrence launches, window_ms the whole of recurrence and contractions
+ * (window_ms - kernel_ms = the contractions' time).  Ends a Lanczos run or a subspace block on the handle.  Whole
+ * matrices only (not slabs).
+ */
+int bdg_green_bond_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
+                          const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* out);
 
 /*
  * Chebyshev moments of the resolvent between extended states, for G(eps) in plane waves, wave packets or orbitals
