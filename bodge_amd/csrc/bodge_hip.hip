@@ -14,6 +14,8 @@
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
 //   family.hpp      the two tile loops, dispatch, launch plan and set-up shared by fermi / apply / correlation /
 //                   response_map / green / green_map / green_bonds / green_states.hpp
+//   green_driver.hpp  set-up and the batches x ranges x moments loop shared by green / green_map / green_bonds /
+//                   green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
 //   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver
@@ -66,6 +68,7 @@
 #include "apply.hpp"
 #include "correlation.hpp"
 #include "response_map.hpp"
+#include "green_driver.hpp"
 #include "green.hpp"
 #include "green_map.hpp"
 #include "green_bonds.hpp"

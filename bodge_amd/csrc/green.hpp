@@ -75,7 +75,64 @@ namespace {
 
 using GreenKernels = FamilyKernels<bdg::GreenTail>;
 
-constexpr size_t kGreenTableBytes = (size_t)256 << 20;  // device moment table: a range of moments at a time
+// bdg_green_moments on the range loop of green_driver.hpp.  A batch is `width` source rows; the device table is
+// [moment of the range][target][component][vector of the batch], copied into the caller's table when it is full.
+struct GreenPicked : GreenFeature {
+    using Args = bdg::GreenArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::green;
+    bdg_system* sys;
+    const GreenSetup<GreenKernels>& gs;
+    int width, n_sources, n_targets;
+    const int64_t* source_rows;
+    const int32_t* target_block_rows;
+    const std::vector<int32_t>& slot_of;
+    double2* out;
+    double launch_bytes;
+    DeviceBuffer<int> d_slot, d_targets;
+    DeviceBuffer<int64_t> d_rows;
+    DeviceBuffer<double2> d_table;
+    int v0 = 0, n_active = 0;  // the batch in flight: its first source, its sources
+
+    size_t per_moment() const { return (size_t)n_targets * 4 * (size_t)n_active; }
+    int upload(hipStream_t st) {
+        const int64_t nb = sys->nb;
+        if (int rc = d_slot.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
+        if (int rc = d_targets.reserve((size_t)n_targets)) return rc;
+        if (int rc = d_rows.reserve((size_t)n_sources)) return rc;
+        if (int rc = d_table.reserve((size_t)gs.range * n_targets * 4 * (size_t)width)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_slot.ptr, slot_of.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_targets.ptr, target_block_rows, sizeof(int) * n_targets, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_rows.ptr, source_rows, sizeof(int64_t) * n_sources, hipMemcpyHostToDevice, st));
+        return BDG_OK;
+    }
+    int start_batch(int b, double2* cur, double2* prev, Args* ga, hipStream_t st) {
+        v0 = b * width;
+        n_active = std::min(width, n_sources - v0);
+        ga->target_slot = d_slot.ptr;
+        ga->n_active = n_active;
+        green_unit_start(sys, gs, cur, prev, d_rows.ptr + v0, n_active, st);
+        return n_active;
+    }
+    void moment0(const double2* cur, hipStream_t st) {
+        const int grid = (int)std::min<size_t>(1024, (per_moment() + 255) / 256);
+        if (gs.mode.real)
+            bdg::green_pick<2><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, d_targets.ptr, n_targets, n_active, d_table.ptr);
+        else
+            bdg::green_pick<1><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, d_targets.ptr, n_targets, n_active, d_table.ptr);
+    }
+    void point(Args* ga, int m) { ga->table = d_table.ptr + (size_t)m * per_moment(); }
+    int end_range(int n0, int n1, hipStream_t st) {
+        // rows (moment, target, component) of n_active entries into the caller's rows of n_sources
+        return green_copy_out(out + (size_t)n0 * n_targets * 4 * (size_t)n_sources + v0, (size_t)n_sources, d_table.ptr,
+                              (size_t)n_active, (size_t)(n1 - n0) * n_targets * 4, st);
+    }
+    void release() {
+        d_slot.release();
+        d_targets.release();
+        d_rows.release();
+        d_table.release();
+    }
+};
 
 int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_sources, const int64_t* source_rows,
                       int n_targets, const int32_t* target_block_rows, double* out) {
@@ -99,149 +156,19 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
         if (slot_of[(size_t)j] >= 0) return fail(BDG_EINVAL, "target block row %d is listed twice", j);
         slot_of[(size_t)j] = t;
     }
-    lanczos_free(sys);
+    lanczos_free(sys);  // (no subspace_free here, unlike run_green_bond_blocks: kept as it was)
     HIP_TRY(hipSetDevice(sys->device));
 
-    // Arithmetic and storage mode as for a recurrence with unit start vectors.
+    // Arithmetic and storage mode as for a recurrence with unit start vectors; a batch is `width` source rows.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
-    // Source rows per batch: the widest power of two up to 64 whose vector buffer stays within 96 MB
-    // (batch_width's rule for the one-step kernels); set_lanes_per_row fixes the lanes instead.
-    const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
-    int width = 64;
-    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
-    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
-    width = std::min(width, n_sources);
-    int rl = std::max(4, next_pow2((width + per_lane - 1) / per_lane));
-    if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= width) rl = sys->lanes_override;
-    const int rv = rl * per_lane;
-    FamilyPlan<GreenKernels::Kernel> gplan;
-    if (int rc = make_family_plan<GreenKernels>(sys, rl, mode, 0, &gplan)) return rc;
-    const StepPlan& plan = gplan.step;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, (real ? 32.0 : 64.0) * rv, &base.tile_order,
-                                    &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
-    const int n_batches = (n_sources + width - 1) / width;
-
-    // Device table: [moment of the range][target][component][vector of the batch]; a range of moments whose
-    // entries fit the limit, copied into the caller's table when it is full.
-    size_t limit = kGreenTableBytes;
-    if (const char* env = knob::raw("BODGE_AMD_GREEN_TABLE_BYTES")) limit = (size_t)std::max(1LL, atoll(env));
-    const size_t per_moment_max = (size_t)n_targets * 4 * (size_t)width;  // double2 entries of one moment
-    const int range = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moments, limit / (per_moment_max * sizeof(double2))));
-    const int n_ranges = (n_moments + range - 1) / range;
-
-    if (int rc = sys->vec_a.reserve(vec_count)) return rc;
-    if (int rc = sys->vec_b.reserve(vec_count)) return rc;
-    DeviceBuffer<int> d_slot, d_targets;
-    DeviceBuffer<int64_t> d_rows;
-    DeviceBuffer<double2> d_table;
-    std::vector<hipEvent_t> events;
-    auto body = [&]() -> int {
-        if (int rc = d_slot.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
-        if (int rc = d_targets.reserve((size_t)n_targets)) return rc;
-        if (int rc = d_rows.reserve((size_t)n_sources)) return rc;
-        if (int rc = d_table.reserve((size_t)range * per_moment_max)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_slot.ptr, slot_of.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_targets.ptr, target_block_rows, sizeof(int) * n_targets, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_rows.ptr, source_rows, sizeof(int64_t) * n_sources, hipMemcpyHostToDevice, st));
-        events.assign((size_t)2 * n_batches * n_ranges, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        bdg_perf perf{};
-        for (int b = 0; b < n_batches; ++b) {
-            const int v0 = b * width;
-            const int n_active = std::min(width, n_sources - v0);
-            const size_t per_moment = (size_t)n_targets * 4 * (size_t)n_active;
-            bdg::GreenArgs ga{};
-            ga.s = base;
-            ga.target_slot = d_slot.ptr;
-            ga.n_active = n_active;
-            double2* cur = sys->vec_a.ptr;
-            double2* prev = sys->vec_b.ptr;
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(cur, (int64_t)vec_count);
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
-            if (real)
-                bdg::set_unit_real<<<1, 64, 0, st>>>(reinterpret_cast<double*>(cur), nb, nb, rv, n_active,
-                                                     d_rows.ptr + v0, (int64_t)0);
-            else
-                bdg::set_unit<<<1, 64, 0, st>>>(cur, nb, nb, rv, n_active, d_rows.ptr + v0, (int64_t)0);
-            for (int g = 0; g < n_ranges; ++g) {
-                const int n0 = g * range, n1 = std::min(n_moments, n0 + range);
-                const size_t ev = (size_t)2 * (b * n_ranges + g);
-                HIP_TRY(hipEventRecord(events[ev], st));
-                for (int n = n0; n < n1; ++n) {
-                    double2* slice = d_table.ptr + (size_t)(n - n0) * per_moment;
-                    if (n == 0) {
-                        // mu_0 from t_0 itself
-                        const int grid = (int)std::min<size_t>(1024, (per_moment + 255) / 256);
-                        if (real)
-                            bdg::green_pick<2><<<grid, 256, 0, st>>>(cur, nb, rl, d_targets.ptr, n_targets, n_active, slice);
-                        else
-                            bdg::green_pick<1><<<grid, 256, 0, st>>>(cur, nb, rl, d_targets.ptr, n_targets, n_active, slice);
-                        continue;
-                    }
-                    // t_1 = H~ t_0 (t_{-1} = 0), then t_{n+1} = 2 H~ t_n - t_{n-1}: the new vector replaces prev
-                    ga.s.cur = cur;
-                    ga.s.prev = prev;
-                    ga.s.coef = (n == 1 ? 1.0 : 2.0) / scale;
-                    ga.s.reverse = alternate ? (n & 1) : 0;
-                    ga.table = slice;
-                    gplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ga);
-                    std::swap(cur, prev);
-                }
-                HIP_TRY(hipEventRecord(events[ev + 1], st));
-                HIP_TRY(hipGetLastError());
-                // rows (moment, target, component) of n_active entries into the caller's rows of n_sources
-                double2* dst = reinterpret_cast<double2*>(out) + (size_t)n0 * n_targets * 4 * (size_t)n_sources + v0;
-                if (n_active == n_sources)
-                    HIP_TRY(hipMemcpyAsync(dst, d_table.ptr, sizeof(double2) * (size_t)(n1 - n0) * per_moment,
-                                           hipMemcpyDeviceToHost, st));
-                else
-                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double2) * (size_t)n_sources, d_table.ptr,
-                                             sizeof(double2) * (size_t)n_active, sizeof(double2) * (size_t)n_active,
-                                             (size_t)(n1 - n0) * n_targets * 4, hipMemcpyDeviceToHost, st));
-            }
-            perf.vector_steps += (int64_t)(n_moments - 1) * n_active;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t e = 0; e < events.size(); e += 2) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[e], events[e + 1]));
-            perf.kernel_ms += t;
-        }
-        float window = 0.f;
-        HIP_TRY(hipEventElapsedTime(&window, events.front(), events.back()));
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * (n_moments - 1);
-        perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 4.0 * (double)nb +
-                                (double)(per_moment_max * sizeof(double2));
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
-        perf.green = plan.dictionary ? 2 : 1;
-        perf.green_ranges = n_ranges;
-        sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) (void)hipStreamSynchronize(sys->stream);
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_slot.release();
-    d_targets.release();
-    d_rows.release();
-    d_table.release();
-    return rc;
+    const GreenWidth lanes = green_unit_width(sys, mode, n_sources);
+    GreenSetup<GreenKernels> gs;
+    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
+    const size_t moment_bytes = (size_t)n_targets * 4 * (size_t)lanes.width * sizeof(double2);  // one moment of a full batch
+    green_cut_ranges(n_moments, moment_bytes, &gs);
+    GreenPicked feature{{}, sys, gs, lanes.width, n_sources, n_targets, source_rows, target_block_rows, slot_of,
+                        reinterpret_cast<double2*>(out), 4.0 * (double)nb + (double)moment_bytes};
+    return run_green_ranges(sys, gs, scale, n_moments, (n_sources + lanes.width - 1) / lanes.width, feature);
 }
 
 }  // namespace

@@ -154,6 +154,106 @@ namespace {
 
 using GreenBondKernels = FamilyKernels<bdg::GreenBondTail>;
 
+// bdg_green_bond_blocks on the range loop of green_driver.hpp.  A batch is `batch_sites` whole column sites; the device
+// table is [moment of the range][block of the batch][component][column], contracted into the result on the device
+// when it is full.  The third event of a range closes its contraction: window_ms - kernel_ms is the contractions' time.
+struct GreenBonds : GreenFeature {
+    using Args = bdg::GreenBondArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::green_bonds;
+    static constexpr int kEvents = 3;
+    bdg_system* sys;
+    const GreenSetup<GreenBondKernels>& gs;
+    int batch_sites, n_sites, n_components, n_moments, n_weights;
+    const double* weights;
+    const int32_t* pat_indptr;
+    const std::vector<int2>& entry;
+    const std::vector<int32_t>& block_row;
+    const std::vector<int32_t>& batch_blocks;
+    const std::vector<int64_t>& batch_ptr;
+    const std::vector<int64_t>& start_rows;
+    int64_t max_blocks;
+    double* out;
+    double launch_bytes;
+    DeviceBuffer<int> d_indptr, d_block_row, d_batch_blocks;
+    DeviceBuffer<int2> d_entry;
+    DeviceBuffer<int64_t> d_rows;
+    DeviceBuffer<double2> d_table, d_weights, d_out;
+    int s0 = 0, n_slots = 0, n_blocks = 0;  // the batch in flight: its first site, its sites, its blocks
+    const int* blocks_of_batch = nullptr;
+
+    int comp_shift() const { return n_components == 2 ? 1 : 2; }
+    size_t per_block() const { return (size_t)4 * n_components; }  // double2 entries of one block and moment
+    size_t per_moment() const { return (size_t)n_blocks * per_block(); }
+    size_t out_count() const { return (size_t)n_weights * entry.size() * 16; }
+    int upload(hipStream_t st) {
+        const size_t nb = (size_t)sys->nb, n_pat = entry.size();
+        if (int rc = d_indptr.reserve(nb + 1)) return rc;
+        if (int rc = d_block_row.reserve(n_pat)) return rc;
+        if (int rc = d_batch_blocks.reserve(n_pat)) return rc;
+        if (int rc = d_entry.reserve(n_pat)) return rc;
+        if (int rc = d_rows.reserve(start_rows.size())) return rc;
+        if (int rc = d_table.reserve((size_t)gs.range * max_blocks * per_block())) return rc;
+        if (int rc = d_weights.reserve((size_t)n_weights * n_moments)) return rc;
+        if (int rc = d_out.reserve(out_count())) return rc;
+        HIP_TRY(hipMemcpyAsync(d_indptr.ptr, pat_indptr, sizeof(int) * (nb + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_block_row.ptr, block_row.data(), sizeof(int) * n_pat, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_batch_blocks.ptr, batch_blocks.data(), sizeof(int) * n_pat, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_entry.ptr, entry.data(), sizeof(int2) * n_pat, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_rows.ptr, start_rows.data(), sizeof(int64_t) * start_rows.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_weights.ptr, weights, sizeof(double2) * (size_t)n_weights * n_moments, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_out.ptr, 0, sizeof(double2) * out_count(), st));
+        return BDG_OK;
+    }
+    int start_batch(int b, double2* cur, double2* prev, Args* ga, hipStream_t st) {
+        s0 = b * batch_sites;
+        n_slots = std::min(batch_sites, n_sites - s0);
+        n_blocks = (int)(batch_ptr[(size_t)b + 1] - batch_ptr[(size_t)b]);
+        blocks_of_batch = d_batch_blocks.ptr + batch_ptr[(size_t)b];
+        ga->pat_indptr = d_indptr.ptr;
+        ga->pat_entry = d_entry.ptr;
+        ga->slot_base = s0;
+        ga->n_slots = n_slots;
+        ga->comp_shift = comp_shift();
+        green_unit_start(sys, gs, cur, prev, d_rows.ptr + (size_t)s0 * n_components, n_slots * n_components, st);
+        return n_slots * n_components;
+    }
+    void moment0(const double2* cur, hipStream_t st) {
+        const int grid = (int)std::min<size_t>(1024, (per_moment() + 255) / 256);
+        if (gs.mode.real)
+            bdg::green_bond_pick<2><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, blocks_of_batch, d_block_row.ptr, d_entry.ptr,
+                                                          n_blocks, s0, comp_shift(), d_table.ptr);
+        else
+            bdg::green_bond_pick<1><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, blocks_of_batch, d_block_row.ptr, d_entry.ptr,
+                                                          n_blocks, s0, comp_shift(), d_table.ptr);
+    }
+    void point(Args* ga, int m) { ga->table = d_table.ptr + (size_t)m * per_moment(); }
+    int end_range(int n0, int n1, hipStream_t st) {
+        // the range's moments into the result: the sums go on where the range before left them
+        const dim3 grid((unsigned)((per_moment() + 255) / 256), (unsigned)((n_weights + bdg::kBondEnergies - 1) / bdg::kBondEnergies));
+        if (n_components == 2)
+            bdg::green_bond_contract<2><<<grid, 256, 0, st>>>(d_table.ptr, n0, n1, (int)per_moment(), d_weights.ptr, n_moments,
+                                                             n_weights, blocks_of_batch, (int64_t)entry.size(), d_out.ptr);
+        else
+            bdg::green_bond_contract<4><<<grid, 256, 0, st>>>(d_table.ptr, n0, n1, (int)per_moment(), d_weights.ptr, n_moments,
+                                                             n_weights, blocks_of_batch, (int64_t)entry.size(), d_out.ptr);
+        return BDG_OK;
+    }
+    int finish(hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(out, d_out.ptr, sizeof(double2) * out_count(), hipMemcpyDeviceToHost, st));
+        return BDG_OK;
+    }
+    void release() {
+        d_indptr.release();
+        d_block_row.release();
+        d_batch_blocks.release();
+        d_entry.release();
+        d_rows.release();
+        d_table.release();
+        d_weights.release();
+        d_out.release();
+    }
+};
+
 int run_green_bond_blocks(bdg_system* sys, double scale, int n_moments, int n_weights, const double* weights,
                           const int32_t* pat_indptr, const int32_t* pat_indices, int n_components, double* out) {
     // (argument errors first, in the order of the header; none of them needs a GPU)
@@ -181,11 +281,10 @@ int run_green_bond_blocks(bdg_system* sys, double scale, int n_moments, int n_we
     if (sys->ncols != sys->nb || sys->row_offset != 0)
         return fail(BDG_EINVAL, "bdg_green_bond_blocks needs a whole (square) matrix: slabs are not supported");
     lanczos_free(sys);
-    subspace_free(sys);
+    subspace_free(sys);  // (this driver alone of the four ends a subspace block as well: kept as it was)
     HIP_TRY(hipSetDevice(sys->device));
 
     // The column sites of the call: the distinct columns of the pattern, ascending.
-    const int comp_shift = n_components == 2 ? 1 : 2;
     std::vector<int32_t> position((size_t)nb, -1);
     for (int64_t k = 0; k < n_pat; ++k) position[(size_t)pat_indices[k]] = 0;
     std::vector<int32_t> sites;
@@ -199,33 +298,13 @@ int run_green_bond_blocks(bdg_system* sys, double scale, int n_moments, int n_we
     for (int s = 0; s < n_sites; ++s)
         for (int b = 0; b < n_components; ++b) start_rows[(size_t)s * n_components + b] = 4 * (int64_t)sites[(size_t)s] + b;
 
-    // Arithmetic and storage mode, width and lanes exactly as in run_green_local_moments.
+    // Arithmetic and storage mode as for a recurrence with unit start vectors; a batch holds whole sites.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
-    const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
-    int width = 64;
-    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
-    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
-    width = std::min(width, n_sites * n_components);
-    int rl = std::max(4, next_pow2((width + per_lane - 1) / per_lane));
-    if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= width) rl = sys->lanes_override;
-    const int rv = rl * per_lane;
-    const int batch_sites = width / n_components;
-    FamilyPlan<GreenBondKernels::Kernel> gplan;
-    if (int rc = make_family_plan<GreenBondKernels>(sys, rl, mode, 0, &gplan)) return rc;
-    const StepPlan& plan = gplan.step;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, (real ? 32.0 : 64.0) * rv, &base.tile_order,
-                                    &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
+    const GreenWidth lanes = green_unit_width(sys, mode, n_sites * n_components);
+    const int batch_sites = lanes.width / n_components;
     const int n_batches = (n_sites + batch_sites - 1) / batch_sites;
+    GreenSetup<GreenBondKernels> gs;
+    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
 
     // The pattern's blocks by batch: a block belongs to the batch of its column site and has an index in that batch's
     // table; batch_blocks lists the blocks of batch b (pattern order) from batch_ptr[b] on.
@@ -249,142 +328,12 @@ int run_green_bond_blocks(bdg_system* sys, double scale, int n_moments, int n_we
     int64_t max_blocks = 0;
     for (int b = 0; b < n_batches; ++b) max_blocks = std::max(max_blocks, batch_ptr[(size_t)b + 1] - batch_ptr[(size_t)b]);
 
-    // Device table: [moment of the range][block of the batch][component][column]; a range of moments whose entries
-    // fit the limit, contracted into the result when it is full.
-    size_t limit = kGreenTableBytes;
-    if (const char* env = knob::raw("BODGE_AMD_GREEN_TABLE_BYTES")) limit = (size_t)std::max(1LL, atoll(env));
-    const size_t per_block = (size_t)4 * n_components;  // double2 entries of one block and moment
-    const size_t per_moment_max = (size_t)max_blocks * per_block;
-    const int range = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moments, limit / (per_moment_max * sizeof(double2))));
-    const int n_ranges = (n_moments + range - 1) / range;
-    const size_t out_count = (size_t)n_weights * (size_t)n_pat * 16;
-
-    if (int rc = sys->vec_a.reserve(vec_count)) return rc;
-    if (int rc = sys->vec_b.reserve(vec_count)) return rc;
-    DeviceBuffer<int> d_indptr, d_block_row, d_batch_blocks;
-    DeviceBuffer<int2> d_entry;
-    DeviceBuffer<int64_t> d_rows;
-    DeviceBuffer<double2> d_table, d_weights, d_out;
-    std::vector<hipEvent_t> events;
-    auto body = [&]() -> int {
-        if (int rc = d_indptr.reserve((size_t)nb + 1)) return rc;
-        if (int rc = d_block_row.reserve((size_t)n_pat)) return rc;
-        if (int rc = d_batch_blocks.reserve((size_t)n_pat)) return rc;
-        if (int rc = d_entry.reserve((size_t)n_pat)) return rc;
-        if (int rc = d_rows.reserve(start_rows.size())) return rc;
-        if (int rc = d_table.reserve((size_t)range * per_moment_max)) return rc;
-        if (int rc = d_weights.reserve((size_t)n_weights * n_moments)) return rc;
-        if (int rc = d_out.reserve(out_count)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_indptr.ptr, pat_indptr, sizeof(int) * ((size_t)nb + 1), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_block_row.ptr, block_row.data(), sizeof(int) * (size_t)n_pat, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_batch_blocks.ptr, batch_blocks.data(), sizeof(int) * (size_t)n_pat, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_entry.ptr, entry.data(), sizeof(int2) * (size_t)n_pat, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_rows.ptr, start_rows.data(), sizeof(int64_t) * start_rows.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_weights.ptr, weights, sizeof(double2) * (size_t)n_weights * n_moments, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_out.ptr, 0, sizeof(double2) * out_count, st));
-        events.assign((size_t)3 * n_batches * n_ranges, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        bdg_perf perf{};
-        for (int b = 0; b < n_batches; ++b) {
-            const int s0 = b * batch_sites;
-            const int n_slots = std::min(batch_sites, n_sites - s0);
-            const int n_active = n_slots * n_components;
-            const int n_blocks = (int)(batch_ptr[(size_t)b + 1] - batch_ptr[(size_t)b]);
-            const int* blocks_of_batch = d_batch_blocks.ptr + batch_ptr[(size_t)b];
-            const size_t per_moment = (size_t)n_blocks * per_block;
-            bdg::GreenBondArgs ga{};
-            ga.s = base;
-            ga.pat_indptr = d_indptr.ptr;
-            ga.pat_entry = d_entry.ptr;
-            ga.slot_base = s0;
-            ga.n_slots = n_slots;
-            ga.comp_shift = comp_shift;
-            double2* cur = sys->vec_a.ptr;
-            double2* prev = sys->vec_b.ptr;
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(cur, (int64_t)vec_count);
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
-            const int64_t* rows = d_rows.ptr + (size_t)s0 * n_components;
-            if (real)
-                bdg::set_unit_real<<<1, 64, 0, st>>>(reinterpret_cast<double*>(cur), nb, nb, rv, n_active, rows, (int64_t)0);
-            else
-                bdg::set_unit<<<1, 64, 0, st>>>(cur, nb, nb, rv, n_active, rows, (int64_t)0);
-            for (int g = 0; g < n_ranges; ++g) {
-                const int n0 = g * range, n1 = std::min(n_moments, n0 + range);
-                const size_t ev = (size_t)3 * (b * n_ranges + g);
-                HIP_TRY(hipEventRecord(events[ev], st));
-                for (int n = n0; n < n1; ++n) {
-                    double2* slice = d_table.ptr + (size_t)(n - n0) * per_moment;
-                    if (n == 0) {
-                        // mu_0 from t_0 itself
-                        const int grid = (int)std::min<size_t>(1024, (per_moment + 255) / 256);
-                        if (real)
-                            bdg::green_bond_pick<2><<<grid, 256, 0, st>>>(cur, nb, rl, blocks_of_batch, d_block_row.ptr,
-                                                                          d_entry.ptr, n_blocks, s0, comp_shift, slice);
-                        else
-                            bdg::green_bond_pick<1><<<grid, 256, 0, st>>>(cur, nb, rl, blocks_of_batch, d_block_row.ptr,
-                                                                          d_entry.ptr, n_blocks, s0, comp_shift, slice);
-                        continue;
-                    }
-                    // t_1 = H~ t_0 (t_{-1} = 0), then t_{n+1} = 2 H~ t_n - t_{n-1}: the new vector replaces prev
-                    ga.s.cur = cur;
-                    ga.s.prev = prev;
-                    ga.s.coef = (n == 1 ? 1.0 : 2.0) / scale;
-                    ga.s.reverse = alternate ? (n & 1) : 0;
-                    ga.table = slice;
-                    gplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ga);
-                    std::swap(cur, prev);
-                }
-                HIP_TRY(hipEventRecord(events[ev + 1], st));
-                // the range's moments into the result: the sums go on where the range before left them
-                const dim3 grid((unsigned)((per_moment + 255) / 256), (unsigned)((n_weights + bdg::kBondEnergies - 1) / bdg::kBondEnergies));
-                if (n_components == 2)
-                    bdg::green_bond_contract<2><<<grid, 256, 0, st>>>(d_table.ptr, n0, n1, (int)per_moment, d_weights.ptr,
-                                                                     n_moments, n_weights, blocks_of_batch, n_pat, d_out.ptr);
-                else
-                    bdg::green_bond_contract<4><<<grid, 256, 0, st>>>(d_table.ptr, n0, n1, (int)per_moment, d_weights.ptr,
-                                                                     n_moments, n_weights, blocks_of_batch, n_pat, d_out.ptr);
-                HIP_TRY(hipEventRecord(events[ev + 2], st));
-                HIP_TRY(hipGetLastError());
-            }
-            perf.vector_steps += (int64_t)(n_moments - 1) * n_active;
-        }
-        HIP_TRY(hipMemcpyAsync(out, d_out.ptr, sizeof(double2) * out_count, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t e = 0; e < events.size(); e += 3) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[e], events[e + 1]));
-            perf.kernel_ms += t;
-        }
-        // (the window runs to the end of the last contraction: window_ms - kernel_ms is the contractions' time)
-        float window = 0.f;
-        HIP_TRY(hipEventElapsedTime(&window, events.front(), events.back()));
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * (n_moments - 1);
-        perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 4.0 * (double)(nb + 1) +
-                                (double)max_blocks * sizeof(int2) + (double)(per_moment_max * sizeof(double2));
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
-        perf.green_ranges = n_ranges;
-        perf.green_bonds = plan.dictionary ? 2 : 1;
-        sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) (void)hipStreamSynchronize(sys->stream);
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_indptr.release();
-    d_block_row.release();
-    d_batch_blocks.release();
-    d_entry.release();
-    d_rows.release();
-    d_table.release();
-    d_weights.release();
-    d_out.release();
-    return rc;
+    const size_t moment_bytes = (size_t)max_blocks * 4 * n_components * sizeof(double2);  // one moment of the largest batch
+    green_cut_ranges(n_moments, moment_bytes, &gs);
+    GreenBonds feature{{}, sys, gs, batch_sites, n_sites, n_components, n_moments, n_weights, weights, pat_indptr, entry,
+                       block_row, batch_blocks, batch_ptr, start_rows, max_blocks, out,
+                       4.0 * (double)(nb + 1) + (double)max_blocks * sizeof(int2) + (double)moment_bytes};
+    return run_green_ranges(sys, gs, scale, n_moments, n_batches, feature);
 }
 
 }  // namespace

@@ -82,6 +82,69 @@ namespace {
 
 using GreenLocalKernels = FamilyKernels<bdg::GreenLocalTail>;
 
+// bdg_green_local_moments on the range loop of green_driver.hpp.  A batch is `batch_sites` whole sites; the device
+// table is [moment of the range][site of the batch][component][column], copied into the caller's table when it is full.
+struct GreenLocal : GreenFeature {
+    using Args = bdg::GreenLocalArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::green_local;
+    bdg_system* sys;
+    const GreenSetup<GreenLocalKernels>& gs;
+    int batch_sites, n_sites, n_components;
+    const int32_t* block_rows;
+    const std::vector<int32_t>& position;
+    const std::vector<int64_t>& start_rows;
+    double2* out;
+    double launch_bytes;
+    DeviceBuffer<int> d_position, d_sites;
+    DeviceBuffer<int64_t> d_rows;
+    DeviceBuffer<double2> d_table;
+    int s0 = 0, n_slots = 0;  // the batch in flight: its first site, its sites
+
+    int comp_shift() const { return n_components == 2 ? 1 : 2; }
+    size_t per_site() const { return (size_t)4 * n_components; }  // double2 entries of one site and moment
+    size_t per_moment() const { return (size_t)n_slots * per_site(); }
+    int upload(hipStream_t st) {
+        const int64_t nb = sys->nb;
+        if (int rc = d_position.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
+        if (int rc = d_sites.reserve((size_t)n_sites)) return rc;
+        if (int rc = d_rows.reserve(start_rows.size())) return rc;
+        if (int rc = d_table.reserve((size_t)gs.range * batch_sites * per_site())) return rc;
+        HIP_TRY(hipMemcpyAsync(d_position.ptr, position.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_sites.ptr, block_rows, sizeof(int) * n_sites, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_rows.ptr, start_rows.data(), sizeof(int64_t) * start_rows.size(), hipMemcpyHostToDevice, st));
+        return BDG_OK;
+    }
+    int start_batch(int b, double2* cur, double2* prev, Args* ga, hipStream_t st) {
+        s0 = b * batch_sites;
+        n_slots = std::min(batch_sites, n_sites - s0);
+        ga->site_slot = d_position.ptr;
+        ga->slot_base = s0;
+        ga->n_slots = n_slots;
+        ga->comp_shift = comp_shift();
+        green_unit_start(sys, gs, cur, prev, d_rows.ptr + (size_t)s0 * n_components, n_slots * n_components, st);
+        return n_slots * n_components;
+    }
+    void moment0(const double2* cur, hipStream_t st) {
+        const int grid = (int)std::min<size_t>(1024, (per_moment() + 255) / 256);
+        if (gs.mode.real)
+            bdg::green_local_pick<2><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, d_sites.ptr + s0, n_slots, comp_shift(), d_table.ptr);
+        else
+            bdg::green_local_pick<1><<<grid, 256, 0, st>>>(cur, sys->nb, gs.rl, d_sites.ptr + s0, n_slots, comp_shift(), d_table.ptr);
+    }
+    void point(Args* ga, int m) { ga->table = d_table.ptr + (size_t)m * per_moment(); }
+    int end_range(int n0, int n1, hipStream_t st) {
+        // rows (moment) of the batch's n_slots sites into the caller's rows of n_sites sites
+        return green_copy_out(out + ((size_t)n0 * n_sites + s0) * per_site(), (size_t)n_sites * per_site(), d_table.ptr,
+                              per_moment(), (size_t)(n1 - n0), st);
+    }
+    void release() {
+        d_position.release();
+        d_sites.release();
+        d_rows.release();
+        d_table.release();
+    }
+};
+
 int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_sites, const int32_t* block_rows,
                             int n_components, double* out) {
     if (!sys) return fail(BDG_EINVAL, "null system handle");
@@ -93,7 +156,6 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
     if (n_sites < 1) return fail(BDG_EINVAL, "n_sites must be >= 1");
     if (n_components != 2 && n_components != 4) return fail(BDG_EINVAL, "n_components must be 2 or 4");
     const int64_t nb = sys->nb;
-    const int comp_shift = n_components == 2 ? 1 : 2;
     // position of every block row in the site list; a block row is listed once (one writer per table entry)
     std::vector<int32_t> position((size_t)nb, -1);
     std::vector<int64_t> start_rows((size_t)n_sites * n_components);
@@ -104,154 +166,20 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
         position[(size_t)j] = s;
         for (int b = 0; b < n_components; ++b) start_rows[(size_t)s * n_components + b] = 4 * (int64_t)j + b;
     }
-    lanczos_free(sys);
+    lanczos_free(sys);  // (no subspace_free here, unlike run_green_bond_blocks: kept as it was)
     HIP_TRY(hipSetDevice(sys->device));
 
-    // Arithmetic and storage mode as for a recurrence with unit start vectors.
+    // Arithmetic and storage mode as for a recurrence with unit start vectors; a batch holds whole sites.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
-    // Vectors per batch: the widest power of two up to 64 whose vector buffer stays within 96 MB (batch_width's
-    // rule for the one-step kernels); set_lanes_per_row fixes the lanes instead.  A batch holds whole sites.
-    const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
-    int width = 64;
-    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
-    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
-    width = std::min(width, n_sites * n_components);
-    int rl = std::max(4, next_pow2((width + per_lane - 1) / per_lane));
-    if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= width) rl = sys->lanes_override;
-    const int rv = rl * per_lane;
-    const int batch_sites = width / n_components;
-    FamilyPlan<GreenLocalKernels::Kernel> gplan;
-    if (int rc = make_family_plan<GreenLocalKernels>(sys, rl, mode, 0, &gplan)) return rc;
-    const StepPlan& plan = gplan.step;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, (real ? 32.0 : 64.0) * rv, &base.tile_order,
-                                    &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
-    const int n_batches = (n_sites + batch_sites - 1) / batch_sites;
-
-    // Device table: [moment of the range][site of the batch][component][column]; a range of moments whose
-    // entries fit the limit, copied into the caller's table when it is full.
-    size_t limit = kGreenTableBytes;
-    if (const char* env = knob::raw("BODGE_AMD_GREEN_TABLE_BYTES")) limit = (size_t)std::max(1LL, atoll(env));
-    const size_t per_site = (size_t)4 * n_components;                   // double2 entries of one site and moment
-    const size_t per_moment_max = (size_t)batch_sites * per_site;
-    const int range = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_moments, limit / (per_moment_max * sizeof(double2))));
-    const int n_ranges = (n_moments + range - 1) / range;
-
-    if (int rc = sys->vec_a.reserve(vec_count)) return rc;
-    if (int rc = sys->vec_b.reserve(vec_count)) return rc;
-    DeviceBuffer<int> d_position, d_sites;
-    DeviceBuffer<int64_t> d_rows;
-    DeviceBuffer<double2> d_table;
-    std::vector<hipEvent_t> events;
-    auto body = [&]() -> int {
-        if (int rc = d_position.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
-        if (int rc = d_sites.reserve((size_t)n_sites)) return rc;
-        if (int rc = d_rows.reserve(start_rows.size())) return rc;
-        if (int rc = d_table.reserve((size_t)range * per_moment_max)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_position.ptr, position.data(), sizeof(int) * nb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_sites.ptr, block_rows, sizeof(int) * n_sites, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_rows.ptr, start_rows.data(), sizeof(int64_t) * start_rows.size(), hipMemcpyHostToDevice, st));
-        events.assign((size_t)2 * n_batches * n_ranges, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        bdg_perf perf{};
-        for (int b = 0; b < n_batches; ++b) {
-            const int s0 = b * batch_sites;
-            const int n_slots = std::min(batch_sites, n_sites - s0);
-            const int n_active = n_slots * n_components;
-            const size_t per_moment = (size_t)n_slots * per_site;
-            bdg::GreenLocalArgs ga{};
-            ga.s = base;
-            ga.site_slot = d_position.ptr;
-            ga.slot_base = s0;
-            ga.n_slots = n_slots;
-            ga.comp_shift = comp_shift;
-            double2* cur = sys->vec_a.ptr;
-            double2* prev = sys->vec_b.ptr;
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(cur, (int64_t)vec_count);
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
-            const int64_t* rows = d_rows.ptr + (size_t)s0 * n_components;
-            if (real)
-                bdg::set_unit_real<<<1, 64, 0, st>>>(reinterpret_cast<double*>(cur), nb, nb, rv, n_active, rows, (int64_t)0);
-            else
-                bdg::set_unit<<<1, 64, 0, st>>>(cur, nb, nb, rv, n_active, rows, (int64_t)0);
-            for (int g = 0; g < n_ranges; ++g) {
-                const int n0 = g * range, n1 = std::min(n_moments, n0 + range);
-                const size_t ev = (size_t)2 * (b * n_ranges + g);
-                HIP_TRY(hipEventRecord(events[ev], st));
-                for (int n = n0; n < n1; ++n) {
-                    double2* slice = d_table.ptr + (size_t)(n - n0) * per_moment;
-                    if (n == 0) {
-                        // mu_0 from t_0 itself
-                        const int grid = (int)std::min<size_t>(1024, (per_moment + 255) / 256);
-                        if (real)
-                            bdg::green_local_pick<2><<<grid, 256, 0, st>>>(cur, nb, rl, d_sites.ptr + s0, n_slots, comp_shift, slice);
-                        else
-                            bdg::green_local_pick<1><<<grid, 256, 0, st>>>(cur, nb, rl, d_sites.ptr + s0, n_slots, comp_shift, slice);
-                        continue;
-                    }
-                    // t_1 = H~ t_0 (t_{-1} = 0), then t_{n+1} = 2 H~ t_n - t_{n-1}: the new vector replaces prev
-                    ga.s.cur = cur;
-                    ga.s.prev = prev;
-                    ga.s.coef = (n == 1 ? 1.0 : 2.0) / scale;
-                    ga.s.reverse = alternate ? (n & 1) : 0;
-                    ga.table = slice;
-                    gplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ga);
-                    std::swap(cur, prev);
-                }
-                HIP_TRY(hipEventRecord(events[ev + 1], st));
-                HIP_TRY(hipGetLastError());
-                // rows (moment) of the batch's n_slots sites into the caller's rows of n_sites sites
-                double2* dst = reinterpret_cast<double2*>(out) + ((size_t)n0 * n_sites + s0) * per_site;
-                if (n_slots == n_sites)
-                    HIP_TRY(hipMemcpyAsync(dst, d_table.ptr, sizeof(double2) * (size_t)(n1 - n0) * per_moment,
-                                           hipMemcpyDeviceToHost, st));
-                else
-                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double2) * (size_t)n_sites * per_site, d_table.ptr,
-                                             sizeof(double2) * per_moment, sizeof(double2) * per_moment,
-                                             (size_t)(n1 - n0), hipMemcpyDeviceToHost, st));
-            }
-            perf.vector_steps += (int64_t)(n_moments - 1) * n_active;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t e = 0; e < events.size(); e += 2) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[e], events[e + 1]));
-            perf.kernel_ms += t;
-        }
-        float window = 0.f;
-        HIP_TRY(hipEventElapsedTime(&window, events.front(), events.back()));
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * (n_moments - 1);
-        perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 4.0 * (double)nb +
-                                (double)(per_moment_max * sizeof(double2));
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
-        perf.green_ranges = n_ranges;
-        perf.green_local = plan.dictionary ? 2 : 1;
-        sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) (void)hipStreamSynchronize(sys->stream);
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_position.release();
-    d_sites.release();
-    d_rows.release();
-    d_table.release();
-    return rc;
+    const GreenWidth lanes = green_unit_width(sys, mode, n_sites * n_components);
+    const int batch_sites = lanes.width / n_components;
+    GreenSetup<GreenLocalKernels> gs;
+    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
+    const size_t moment_bytes = (size_t)batch_sites * 4 * n_components * sizeof(double2);  // one moment of a full batch
+    green_cut_ranges(n_moments, moment_bytes, &gs);
+    GreenLocal feature{{}, sys, gs, batch_sites, n_sites, n_components, block_rows, position, start_rows,
+                       reinterpret_cast<double2*>(out), 4.0 * (double)nb + (double)moment_bytes};
+    return run_green_ranges(sys, gs, scale, n_moments, (n_sites + batch_sites - 1) / batch_sites, feature);
 }
 
 }  // namespace

@@ -231,6 +231,69 @@ GreenProjectKernel green_state_project_for(int rl) {
     return nullptr;
 }
 
+// bdg_green_state_moments on the range loop of green_driver.hpp.  A batch is `batch_states` whole states.  Device
+// tables of a range of moments: the workgroups' partials [moment][workgroup][column][component], which the launches
+// fill, and the reduced table [moment][state of the batch][component][column], copied into the caller's when the range
+// is full.
+struct GreenStates : GreenFeature {
+    using Args = bdg::GreenStateArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::green_states;
+    bdg_system* sys;
+    const GreenSetup<GreenStateKernels>& gs;
+    GreenProjectKernel project;
+    int batch_states, n_states, n_components;
+    const double* amplitudes;
+    double2* out;
+    double launch_bytes;
+    DeviceBuffer<double2> d_amplitudes, d_partial, d_table;
+    int q0 = 0, n_slots = 0;  // the batch in flight: its first state, its states
+
+    int comp_shift() const { return n_components == 2 ? 1 : 2; }
+    size_t per_state() const { return (size_t)4 * n_components; }  // double2 entries of one state and moment
+    size_t per_moment() const { return (size_t)n_slots * per_state(); }
+    size_t partial_entries() const { return (size_t)gs.plan.step.grid * gs.rl * 4; }  // double2 entries of one moment's partials
+    const double2* batch_amplitudes() const { return d_amplitudes.ptr + (size_t)q0 * sys->nb; }
+    int upload(hipStream_t st) {
+        if (int rc = d_amplitudes.reserve((size_t)n_states * sys->nb)) return rc;
+        if (int rc = d_partial.reserve((size_t)gs.range * partial_entries())) return rc;
+        if (int rc = d_table.reserve((size_t)gs.range * batch_states * per_state())) return rc;
+        HIP_TRY(hipMemcpyAsync(d_amplitudes.ptr, amplitudes, sizeof(double2) * (size_t)n_states * sys->nb, hipMemcpyHostToDevice, st));
+        return BDG_OK;
+    }
+    int start_batch(int b, double2* cur, double2* prev, Args* ga, hipStream_t st) {
+        q0 = b * batch_states;
+        n_slots = std::min(batch_states, n_states - q0);
+        ga->amplitudes = batch_amplitudes();
+        ga->n_active = n_slots * n_components;
+        ga->comp_shift = comp_shift();
+        const int fill_grid = (int)std::min<size_t>(4096, (gs.vec_count + 255) / 256);
+        bdg::green_state_start<<<fill_grid, 256, 0, st>>>(cur, sys->nb, gs.rl, ga->n_active, comp_shift(), ga->amplitudes);
+        bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)gs.vec_count);
+        return ga->n_active;
+    }
+    void moment0(const double2* cur, hipStream_t st) {
+        project<<<gs.plan.step.grid, bdg::kBlockThreads, 0, st>>>(cur, (int)sys->nb, n_slots * n_components, comp_shift(),
+                                                                  batch_amplitudes(), reinterpret_cast<double*>(d_partial.ptr));
+    }
+    void point(Args* ga, int m) { ga->partial = reinterpret_cast<double*>(d_partial.ptr + (size_t)m * partial_entries()); }
+    void close_range(int n0, int n1, hipStream_t st) {
+        // one launch sums the partials of the whole range
+        const int reduce_chunks = (gs.rl * 4 + 63) / 64;
+        bdg::green_state_reduce<<<(n1 - n0) * reduce_chunks, 256, 0, st>>>(d_partial.ptr, d_table.ptr, gs.plan.step.grid, gs.rl,
+                                                                            n_slots * n_components, comp_shift());
+    }
+    int end_range(int n0, int n1, hipStream_t st) {
+        // rows (moment) of the batch's n_slots states into the caller's rows of n_states states
+        return green_copy_out(out + ((size_t)n0 * n_states + q0) * per_state(), (size_t)n_states * per_state(), d_table.ptr,
+                              per_moment(), (size_t)(n1 - n0), st);
+    }
+    void release() {
+        d_amplitudes.release();
+        d_partial.release();
+        d_table.release();
+    }
+};
+
 int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_states, const double* amplitudes,
                             int n_components, double* out) {
     if (!sys) return fail(BDG_EINVAL, "null system handle");
@@ -242,147 +305,32 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
     if (n_states < 1) return fail(BDG_EINVAL, "n_states must be >= 1");
     if (n_components != 2 && n_components != 4) return fail(BDG_EINVAL, "n_components must be 2 or 4");
     const int64_t nb = sys->nb;
-    const int comp_shift = n_components == 2 ? 1 : 2;
-    lanczos_free(sys);
+    lanczos_free(sys);  // (no subspace_free here, unlike run_green_bond_blocks: kept as it was)
     HIP_TRY(hipSetDevice(sys->device));
 
     // Arithmetic as for apply(): real whenever the matrix is real, the columns complex all the same (Re and Im in
     // the two slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
     // Columns per batch by the width rule of run_apply_series: the widest power of two whose vector buffer stays
     // within 96 MB, at most 64 columns - 32 in real arithmetic; set_lanes_per_row fixes the lanes instead.  A batch
     // holds whole states.
     const double per_column = (double)nb * 4 * 16.0;
-    int width = real ? 32 : 64;
+    int width = mode.real ? 32 : 64;
     while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
     int rl = std::max(4, next_pow2((int)std::min<int64_t>((int64_t)n_states * n_components, width)));
     if (sys->lanes_override >= 4) rl = sys->lanes_override;
-    const int rv = rl * per_lane;
     const int batch_states = rl / n_components;
-    FamilyPlan<GreenStateKernels::Kernel> gplan;
-    if (int rc = make_family_plan<GreenStateKernels>(sys, rl, mode, bdg::GreenStateTail::kExtraLds, &gplan)) return rc;
+    GreenSetup<GreenStateKernels> gs;
+    if (int rc = green_setup(sys, mode, rl, bdg::GreenStateTail::kExtraLds, &gs)) return rc;
     const GreenProjectKernel project = green_state_project_for(rl);
     if (!project) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the projected recurrence kernels", rl);
-    const StepPlan& plan = gplan.step;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
-    const int n_batches = (n_states + batch_states - 1) / batch_states;
 
-    // Device tables of a range of moments: the workgroups' partials [moment][workgroup][column][component] and the
-    // reduced table [moment][state of the batch][component][column]; both count towards the limit, and the reduced
-    // table is copied into the caller's when the range is full.
-    size_t limit = kGreenTableBytes;
-    if (const char* env = knob::raw("BODGE_AMD_GREEN_TABLE_BYTES")) limit = (size_t)std::max(1LL, atoll(env));
-    const size_t per_state = (size_t)4 * n_components;            // double2 entries of one state and moment
-    const size_t per_moment_max = (size_t)batch_states * per_state;
-    const size_t partial_entries = (size_t)plan.grid * rl * 4;     // double2 entries of one moment's partials
-    const int range = (int)std::max<size_t>(
-        1, std::min<size_t>((size_t)n_moments, limit / ((per_moment_max + partial_entries) * sizeof(double2))));
-    const int n_ranges = (n_moments + range - 1) / range;
-
-    if (int rc = sys->vec_a.reserve(vec_count)) return rc;
-    if (int rc = sys->vec_b.reserve(vec_count)) return rc;
-    DeviceBuffer<double2> d_amplitudes, d_partial, d_table;
-    std::vector<hipEvent_t> events;
-    auto body = [&]() -> int {
-        if (int rc = d_amplitudes.reserve((size_t)n_states * nb)) return rc;
-        if (int rc = d_partial.reserve((size_t)range * partial_entries)) return rc;
-        if (int rc = d_table.reserve((size_t)range * per_moment_max)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_amplitudes.ptr, amplitudes, sizeof(double2) * (size_t)n_states * nb, hipMemcpyHostToDevice, st));
-        events.assign((size_t)2 * n_batches * n_ranges, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        const int reduce_chunks = (rl * 4 + 63) / 64;
-        bdg_perf perf{};
-        for (int b = 0; b < n_batches; ++b) {
-            const int q0 = b * batch_states;
-            const int n_slots = std::min(batch_states, n_states - q0);
-            const int n_active = n_slots * n_components;
-            const size_t per_moment = (size_t)n_slots * per_state;
-            bdg::GreenStateArgs ga{};
-            ga.s = base;
-            ga.amplitudes = d_amplitudes.ptr + (size_t)q0 * nb;
-            ga.n_active = n_active;
-            ga.comp_shift = comp_shift;
-            double2* cur = sys->vec_a.ptr;
-            double2* prev = sys->vec_b.ptr;
-            bdg::green_state_start<<<fill_grid, 256, 0, st>>>(cur, nb, rl, n_active, comp_shift, ga.amplitudes);
-            bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
-            for (int g = 0; g < n_ranges; ++g) {
-                const int n0 = g * range, n1 = std::min(n_moments, n0 + range);
-                const size_t ev = (size_t)2 * (b * n_ranges + g);
-                HIP_TRY(hipEventRecord(events[ev], st));
-                for (int n = n0; n < n1; ++n) {
-                    double* partial = reinterpret_cast<double*>(d_partial.ptr + (size_t)(n - n0) * partial_entries);
-                    if (n == 0) {
-                        // mu_0 from t_0 itself
-                        project<<<plan.grid, bdg::kBlockThreads, 0, st>>>(cur, (int)nb, n_active, comp_shift, ga.amplitudes, partial);
-                        continue;
-                    }
-                    // t_1 = H~ t_0 (t_{-1} = 0), then t_{n+1} = 2 H~ t_n - t_{n-1}: the new vector replaces prev
-                    ga.s.cur = cur;
-                    ga.s.prev = prev;
-                    ga.s.coef = (n == 1 ? 1.0 : 2.0) / scale;
-                    ga.s.reverse = alternate ? (n & 1) : 0;
-                    ga.partial = partial;
-                    gplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ga);
-                    std::swap(cur, prev);
-                }
-                // one launch sums the partials of the whole range
-                bdg::green_state_reduce<<<(n1 - n0) * reduce_chunks, 256, 0, st>>>(d_partial.ptr, d_table.ptr, plan.grid, rl,
-                                                                                    n_active, comp_shift);
-                HIP_TRY(hipEventRecord(events[ev + 1], st));
-                HIP_TRY(hipGetLastError());
-                // rows (moment) of the batch's n_slots states into the caller's rows of n_states states
-                double2* dst = reinterpret_cast<double2*>(out) + ((size_t)n0 * n_states + q0) * per_state;
-                if (n_slots == n_states)
-                    HIP_TRY(hipMemcpyAsync(dst, d_table.ptr, sizeof(double2) * (size_t)(n1 - n0) * per_moment,
-                                           hipMemcpyDeviceToHost, st));
-                else
-                    HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double2) * (size_t)n_states * per_state, d_table.ptr,
-                                             sizeof(double2) * per_moment, sizeof(double2) * per_moment,
-                                             (size_t)(n1 - n0), hipMemcpyDeviceToHost, st));
-            }
-            perf.vector_steps += (int64_t)(n_moments - 1) * n_active;
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-        for (size_t e = 0; e < events.size(); e += 2) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[e], events[e + 1]));
-            perf.kernel_ms += t;
-        }
-        float window = 0.f;
-        HIP_TRY(hipEventElapsedTime(&window, events.front(), events.back()));
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * (n_moments - 1);
-        perf.bytes_per_launch = algorithmic_bytes(sys, rv, mode, plan.dictionary) + 16.0 * (double)nb * batch_states +
-                                (double)(partial_entries * sizeof(double2));
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
-        perf.green_ranges = n_ranges;
-        perf.green_states = plan.dictionary ? 2 : 1;
-        sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) (void)hipStreamSynchronize(sys->stream);
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_amplitudes.release();
-    d_partial.release();
-    d_table.release();
-    return rc;
+    // partials and reduced table both count towards the limit of a range
+    const size_t partial_bytes = (size_t)gs.plan.step.grid * rl * 4 * sizeof(double2);
+    green_cut_ranges(n_moments, (size_t)batch_states * 4 * n_components * sizeof(double2) + partial_bytes, &gs);
+    GreenStates feature{{}, sys, gs, project, batch_states, n_states, n_components, amplitudes, reinterpret_cast<double2*>(out),
+                        16.0 * (double)nb * batch_states + (double)partial_bytes};
+    return run_green_ranges(sys, gs, scale, n_moments, (n_states + batch_states - 1) / batch_states, feature);
 }
 
 }  // namespace
