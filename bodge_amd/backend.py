@@ -59,6 +59,7 @@ class Perf(C.Structure):
         ("apply", C.c_int32),
         ("green_states", C.c_int32),
         ("green_bonds", C.c_int32),
+        ("roll_chunk", C.c_int32),
         ("response_map", C.c_int32),
         ("gemm_ms", C.c_double),
         ("gemm_flops", C.c_double),

@@ -714,6 +714,7 @@ struct Batch {
         p.persistent = march ? 1 : 0;
         p.sweeps += march ? sweeps_counted : sweep ? n_launches : 0;
         p.rolling = roll ? 1 : 0;
+        p.roll_chunk = roll ? rplan.args.chunk : 0;  // (what step() gave the batch's last launch)
         p.dict_skipped = sys->dict_skipped;
         p.onsite_streamed = sweep && sys->onsite_streamed ? (sys->bonds_streamed ? 2 : 1) : 0;
         p.lanes_per_row = rl;

@@ -102,6 +102,8 @@ typedef struct bdg_perf {
                               2 = the dictionary kernel (cheb_green_state_dict); 0 = the call was another one */
     int32_t green_bonds;   /* bdg_green_bond_blocks: 1 = its steps ran the streamed-block kernel, 2 = the dictionary kernel
                               (cheb_family / cheb_family_dict with GreenBondTail); 0 = the call was another one */
+    int32_t roll_chunk;    /* cheb_roll3: plane-steps per unit (RollArgs.chunk) of the last rolling launch of the batch the
+                              record describes; 0 = whole-column segments, and 0 when the call did not roll */
     int32_t response_map;  /* bdg_response_map: 1 = the call was this one, 0 = another one */
     double gemm_ms;        /* bdg_response_map: HIP-event time of its product launches (resp_gemm) */
     double gemm_flops;     /* bdg_response_map: 8 x n_moments^2 x K summed over the chunks of sites and the kernels, K = 4 x

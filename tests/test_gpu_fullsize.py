@@ -276,10 +276,16 @@ def test_config4_100cubed_dwave_256_moments_full_length_whole_and_slabs_against_
     f_ref = chebyshev.free_energy_series(chebyshev.dots_to_moments(d_ref, e_ref).mean(axis=1), scale, temperature)
     with DeviceSolver.from_hamiltonian(system) as whole:
         mono = whole.dots_random(scale, moments // 2, vectors, seed=4)
+        mono_perf = whole.perf()
         # two lane groups of 8 vectors side by side on two streams (K8 with 4 lanes per site): the first four are the same vectors
         wide = whole.dots_random(scale, moments // 2, 16, seed=4)
         wide_perf = whole.perf()
     assert wide_perf["rolling"] == 1 and wide_perf["streams"] == 2 and wide_perf["lanes_per_row"] == 4 and wide_perf["launches"] == moments
+    # what config 4 runs: the two lane groups cut their units for equal length (tests/test_gpu_roll_units.py holds that
+    # branch); the 4-vector run, 2 lanes per site, is expected to keep whole-column segments (roll_chunk 0)
+    print(f"[config 4] roll_chunk: 16 vectors {wide_perf['roll_chunk']} (grid {wide_perf['grid']}), "
+          f"4 vectors {mono_perf['roll_chunk']} (lanes {mono_perf['lanes_per_row']}, grid {mono_perf['grid']})")
+    assert wide_perf["roll_chunk"] > 0
     assert np.abs(wide[0][:, :vectors] - d_ref).max() <= 1e-12 * n and np.abs(wide[1][:, :vectors] - e_ref).max() <= 1e-12 * n
     with SlabGroup.from_hamiltonian(system, 8) as group:
         split = group.dots_random(scale, moments // 2, vectors, seed=4)
