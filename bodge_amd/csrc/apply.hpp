@@ -1,7 +1,7 @@
 // apply.hpp - a Chebyshev series of H on caller-supplied vectors, y = Σ_k c_k T_k(H~) x (bdg_apply_series)
 // Part of the single translation unit bodge_hip.hip (included after fermi.hpp): the kernels live in
-// namespace bdg beside the Clenshaw kernels of fermi.hpp, the driver in the unnamed namespace beside
-// run_fermi_blocks.
+// namespace bdg beside the Clenshaw kernels of fermi.hpp, the driver in the unnamed namespace: the feature
+// ApplySeries on the rounds loop of family.hpp (run_family_rounds), which run_fermi_blocks runs too.
 //
 // Clenshaw with a stored source.  Every batch column is a pair (vector v, function f):
 //     b_{M} = b_{M+1} = 0,   b_k = 2 H~ b_{k+1} - b_{k+2} + c_k[f] x_v   (k = M-1 .. 1),
@@ -128,168 +128,83 @@ double apply_bytes(const bdg_system* sys, int vectors, const ModeInfo& mode, boo
            mode.entry_bytes / 3.0 * (double)vectors * (double)sys->nb + 16.0 * n_functions;
 }
 
-// The batch loop of a stored-source series: the columns (vector, function) of the call in batches of the one-step
-// width, every batch staged site-major in vec_d on the way in and on the way out.  `x` and `y_out` are host arrays
-// (bdg_apply_series) or, with `on_device`, device arrays in the same vector-major order (the block of subspace.hpp:
-// the staging buffer is then filled from and emptied to the block; x == y_out is allowed when n_functions == 1, a
-// batch reads and writes its own columns only).  `coef` is on the host in both cases.  `record` = leave the call's
-// figures in sys->perf.
+// A stored-source series on the rounds loop of family.hpp.  A batch is rl columns (vector, function) of the call; per
+// stream set the loop's b_{k+1} / b_{k+2} (vec_a, vec_b), the source x (vec_c) and the site-major staging of the batch's
+// vectors on the way in and of its columns on the way out (vec_d).
+struct ApplySeries : FamilyFeature {
+    using Args = bdg::ApplyArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::apply;
+    static constexpr int kVectors = 4;
+    bdg_system* sys;
+    const FamilySetup<ApplyKernels>& fs;
+    int n_moments, n_functions;
+    int64_t n_columns;
+    const double* coef;
+    const double* x;
+    double* y_out;
+    hipMemcpyKind kind_in, kind_out;
+    bool kRecord;  // not a constant here, though it hides FamilyFeature's: the caller decides (false for bdg_subspace_project)
+    double launch_bytes;
+    DeviceBuffer<double2> d_coef;
+
+    size_t vec_len() const { return (size_t)4 * sys->nb; }  // complex entries of one host vector
+    int upload(hipStream_t st) {
+        if (int rc = d_coef.reserve((size_t)n_moments * n_functions)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_coef.ptr, coef, sizeof(double2) * (size_t)n_moments * n_functions, hipMemcpyHostToDevice, st));
+        return BDG_OK;
+    }
+    int start_batch(int b, StreamSet* set, Args* ca) {
+        ca->x = set->vec_c.ptr;
+        ca->n_functions = n_functions;
+        ca->col_base = b * fs.rl;
+        ca->n_active = (int)std::min<int64_t>(fs.rl, n_columns - (int64_t)ca->col_base);
+        // the vectors this batch's columns belong to: at most rl of them, so they fit the staging buffer
+        const int v_lo = ca->col_base / n_functions;
+        const int v_hi = (ca->col_base + ca->n_active - 1) / n_functions;
+        HIP_TRY(hipMemcpyAsync(set->vec_d.ptr, x + (size_t)2 * vec_len() * v_lo, sizeof(double2) * vec_len() * (size_t)(v_hi - v_lo + 1),
+                               kind_in, set->stream));
+        const int fill_grid = (int)std::min<size_t>(4096, (fs.vec_count + 255) / 256);
+        bdg::apply_scatter<<<fill_grid, 256, 0, set->stream>>>(set->vec_d.ptr, set->vec_c.ptr, sys->nb, fs.rl, ca->n_active,
+                                                                ca->col_base, n_functions, v_lo);
+        return ca->n_active;
+    }
+    void point(Args* ca, int k) { ca->coef_row = d_coef.ptr + (size_t)k * n_functions; }
+    void end_batch(int, StreamSet* set, const double2* y, const Args& ca) {
+        const int64_t total = (int64_t)vec_len() * ca.n_active;
+        const int grid = (int)std::min<int64_t>(4096, (total + 255) / 256);
+        bdg::apply_gather<<<grid, 256, 0, set->stream>>>(y, set->vec_d.ptr, sys->nb, fs.rl, ca.n_active);
+    }
+    int drain_batch(int, StreamSet* set, const Args& ca) {
+        HIP_TRY(hipMemcpyAsync(y_out + (size_t)2 * vec_len() * ca.col_base, set->vec_d.ptr, sizeof(double2) * vec_len() * (size_t)ca.n_active,
+                               kind_out, set->stream));
+        return BDG_OK;
+    }
+    // every stream has carried its own columns to y_out
+    int finish(const std::vector<StreamSet*>& sets, hipStream_t) {
+        for (size_t s = 1; s < sets.size(); ++s) HIP_TRY(hipStreamSynchronize(sets[s]->stream));
+        return BDG_OK;
+    }
+    void release() { d_coef.release(); }
+};
+
+// The columns (vector, function) of the call in batches of the column rule's width (family.hpp).  `x` and `y_out` are
+// host arrays (bdg_apply_series) or, with `on_device`, device arrays in the same vector-major order (the block of
+// subspace.hpp: the staging buffer is then filled from and emptied to the block; x == y_out is allowed when
+// n_functions == 1, a batch reads and writes its own columns only).  `coef` is on the host in both cases.  `record` =
+// leave the call's figures in sys->perf.
 int apply_series_batches(bdg_system* sys, double scale, int n_moments, int n_functions, const double* coef, int n_vectors,
                          const double* x, double* y_out, bool on_device, bool record) {
     const int64_t n_columns = (int64_t)n_vectors * n_functions;
-    const int64_t nb = sys->nb;
-    const hipMemcpyKind kind_in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const hipMemcpyKind kind_out = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-
     // Real arithmetic whenever the matrix is real: the columns may be complex all the same (Re and Im in the two
     // slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
-    // Columns per batch by the one-step width rule: the widest power of two whose vector buffer (16 B per entry
-    // and column) stays within 96 MB, at most 64 columns - 32 in real arithmetic, whose kernels count a column as
-    // two of their 64 vectors; set_lanes_per_row fixes the lanes instead.
-    const double per_column = (double)nb * 4 * 16.0;
-    int width = real ? 32 : 64;
-    while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
-    int rl = std::max(4, next_pow2((int)std::min<int64_t>(n_columns, width)));
-    if (sys->lanes_override >= 4) rl = sys->lanes_override;
-    FamilyPlan<ApplyKernels::Kernel> aplan;
-    if (int rc = make_family_plan<ApplyKernels>(sys, rl, mode, 0, &aplan)) return rc;
-    const StepPlan& plan = aplan.step;
-    const int rv = rl * per_lane;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
-    const int n_batches = (int)((n_columns + rl - 1) / rl);
-
-    // Side by side on two of the handle's stream sets while one launch leaves the GPU part empty (the rule of
-    // run_recurrence for the one-step kernels); BODGE_AMD_STREAMS overrides.
-    int n_streams = (double)nb * rv <= kSideBySideOneStepLimit ? 2 : 1;
-    if (const char* env = knob::raw("BODGE_AMD_STREAMS")) n_streams = std::clamp(atoi(env), 1, 4);
-    n_streams = std::max(1, std::min(n_streams, n_batches));
-    while ((int)sys->side_sets.size() < n_streams - 1) {
-        auto side = std::make_unique<StreamSet>();
-        if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
-        sys->side_sets.push_back(std::move(side));
-    }
-    std::vector<StreamSet*> sets{sys};
-    for (int s = 1; s < n_streams; ++s) sets.push_back(sys->side_sets[(size_t)s - 1].get());
-    // per set: b_{k+1} / b_{k+2} (vec_a, vec_b), the source x (vec_c) and the site-major staging of the batch's
-    // vectors on the way in and of its columns on the way out (vec_d)
-    for (StreamSet* set : sets) {
-        if (int rc = set->vec_a.reserve(vec_count)) return rc;
-        if (int rc = set->vec_b.reserve(vec_count)) return rc;
-        if (int rc = set->vec_c.reserve(vec_count)) return rc;
-        if (int rc = set->vec_d.reserve(vec_count)) return rc;
-    }
-
-    DeviceBuffer<double2> d_coef;
-    std::vector<hipEvent_t> events;
-    const size_t vec_len = (size_t)4 * nb;  // complex entries of one host vector
-    auto body = [&]() -> int {
-        if (int rc = d_coef.reserve((size_t)n_moments * n_functions)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_coef.ptr, coef, sizeof(double2) * (size_t)n_moments * n_functions, hipMemcpyHostToDevice, st));
-        // (tables, packed blocks and the upload above are on the handle's stream: the side streams wait for them)
-        if (!sys->ev_side) HIP_TRY(hipEventCreateWithFlags(&sys->ev_side, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(sys->ev_side, st));
-        for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamWaitEvent(sets[(size_t)s]->stream, sys->ev_side, 0));
-        events.assign((size_t)2 * n_batches, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        bdg_perf perf{};
-        for (int first = 0; first < n_batches; first += n_streams) {
-            const int last = std::min(n_batches, first + n_streams);
-            std::vector<bdg::ApplyArgs> args((size_t)(last - first));
-            std::vector<double2*> cur((size_t)(last - first)), prev((size_t)(last - first));
-            for (int b = first; b < last; ++b) {
-                const size_t q = (size_t)(b - first);
-                StreamSet* set = sets[q];
-                bdg::ApplyArgs& ca = args[q];
-                ca.s = base;
-                ca.x = set->vec_c.ptr;
-                ca.n_functions = n_functions;
-                ca.col_base = b * rl;
-                ca.n_active = (int)std::min<int64_t>(rl, n_columns - (int64_t)ca.col_base);
-                cur[q] = set->vec_a.ptr;
-                prev[q] = set->vec_b.ptr;
-                // the vectors this batch's columns belong to: at most rl of them, so they fit the staging buffer
-                const int v_lo = ca.col_base / n_functions;
-                const int v_hi = (ca.col_base + ca.n_active - 1) / n_functions;
-                HIP_TRY(hipMemcpyAsync(set->vec_d.ptr, x + (size_t)2 * vec_len * v_lo,
-                                       sizeof(double2) * vec_len * (size_t)(v_hi - v_lo + 1), kind_in, set->stream));
-                bdg::apply_scatter<<<fill_grid, 256, 0, set->stream>>>(set->vec_d.ptr, set->vec_c.ptr, nb, rl, ca.n_active,
-                                                                        ca.col_base, n_functions, v_lo);
-                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_a.ptr, (int64_t)vec_count);
-                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_b.ptr, (int64_t)vec_count);
-                HIP_TRY(hipEventRecord(events[(size_t)2 * b], set->stream));
-            }
-            // b_k for k = M-1 .. 1, then y: one launch per coefficient, the batches of the round in turn
-            for (int n = 0; n < n_moments; ++n) {
-                const int k = n_moments - 1 - n;
-                for (int b = first; b < last; ++b) {
-                    const size_t q = (size_t)(b - first);
-                    bdg::ApplyArgs& ca = args[q];
-                    ca.s.cur = cur[q];
-                    ca.s.prev = prev[q];
-                    ca.s.coef = (k == 0 ? 1.0 : 2.0) / scale;
-                    ca.s.reverse = alternate ? (n & 1) : 0;
-                    ca.coef_row = d_coef.ptr + (size_t)k * n_functions;
-                    aplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, sets[q]->stream>>>(ca);
-                    std::swap(cur[q], prev[q]);
-                }
-            }
-            for (int b = first; b < last; ++b) {
-                const size_t q = (size_t)(b - first);
-                HIP_TRY(hipEventRecord(events[(size_t)2 * b + 1], sets[q]->stream));
-                const int64_t total = (int64_t)vec_len * args[q].n_active;
-                const int grid = (int)std::min<int64_t>(4096, (total + 255) / 256);
-                bdg::apply_gather<<<grid, 256, 0, sets[q]->stream>>>(cur[q], sets[q]->vec_d.ptr, nb, rl, args[q].n_active);
-                perf.vector_steps += (int64_t)n_moments * args[q].n_active;
-            }
-            HIP_TRY(hipGetLastError());
-            for (int b = first; b < last; ++b) {
-                const size_t q = (size_t)(b - first);
-                HIP_TRY(hipMemcpyAsync(y_out + (size_t)2 * vec_len * args[q].col_base, sets[q]->vec_d.ptr,
-                                       sizeof(double2) * vec_len * (size_t)args[q].n_active, kind_out, sets[q]->stream));
-            }
-        }
-        for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamSynchronize(sets[(size_t)s]->stream));
-        HIP_TRY(hipStreamSynchronize(st));
-        float window = 0.f;
-        for (int b = 0; b < n_batches; ++b) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[(size_t)2 * b], events[(size_t)2 * b + 1]));
-            perf.kernel_ms += t;
-            HIP_TRY(hipEventElapsedTime(&t, events[0], events[(size_t)2 * b + 1]));
-            window = std::max(window, t);
-        }
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * n_moments;
-        perf.bytes_per_launch = apply_bytes(sys, rv, mode, plan.dictionary, n_functions);
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, n_streams, &perf);
-        perf.apply = plan.dictionary ? 2 : 1;
-        if (record) sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        (void)hipStreamSynchronize(sys->stream);
-        for (auto& side : sys->side_sets) (void)hipStreamSynchronize(side->stream);
-    }
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_coef.release();
-    return rc;
+    FamilySetup<ApplyKernels> fs;
+    if (int rc = family_setup(sys, mode, family_column_lanes(sys, mode, n_columns), 0, &fs)) return rc;
+    ApplySeries feature{{}, sys, fs, n_moments, n_functions, n_columns, coef, x, y_out,
+                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                        on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, record,
+                        apply_bytes(sys, fs.rv, mode, fs.plan.step.dictionary, n_functions)};
+    return run_family_rounds(sys, fs, scale, n_moments, (int)((n_columns + fs.rl - 1) / fs.rl), feature);
 }
 
 int run_apply_series(bdg_system* sys, double scale, int n_moments, int n_functions, const double* coef, int n_vectors,

@@ -12,10 +12,10 @@
 //   plans.hpp       kernel dispatch tables, launch plans (one-step, sweeps, 3-D rolling), stencil tables
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
-//   family.hpp      the two tile loops, dispatch, launch plan and set-up shared by fermi / apply / correlation /
-//                   response_map / green / green_map / green_bonds / green_states.hpp
-//   green_driver.hpp  set-up and the batches x ranges x moments loop shared by green / green_map / green_bonds /
-//                   green_states.hpp
+//   family.hpp      the two tile loops, dispatch, launch plan, width rules and set-up shared by fermi / apply /
+//                   correlation / response_map / green / green_map / green_bonds / green_states.hpp; the rounds of
+//                   batches side by side of fermi / apply
+//   green_driver.hpp  the batches x ranges x moments loop shared by green / green_map / green_bonds / green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
 //   subspace.hpp    a device-resident block of vectors: filter, Gram projection, rotation, residuals
 //   dense.hpp       one-sided Jacobi eigensolver

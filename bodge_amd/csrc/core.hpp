@@ -245,6 +245,21 @@ inline void release_side_sets(bdg_system* sys) {
     }
     sys->side_sets.clear();
 }
+
+// The handle's side sets grown to `n_streams - 1` (streams from the device's pool); with `sets`, the stream sets of a
+// call on n_streams streams: the handle itself, then its side sets in order.
+inline int side_stream_sets(bdg_system* sys, int n_streams, std::vector<StreamSet*>* sets) {
+    while ((int)sys->side_sets.size() < n_streams - 1) {
+        auto side = std::make_unique<StreamSet>();
+        if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
+        sys->side_sets.push_back(std::move(side));
+    }
+    if (sets) {
+        sets->assign(1, sys);
+        for (int s = 1; s < n_streams; ++s) sets->push_back(sys->side_sets[(size_t)s - 1].get());
+    }
+    return BDG_OK;
+}
 }  // namespace
 
 struct bdg_comm {

@@ -1,6 +1,7 @@
 // correlation.hpp - double Chebyshev moments mu[n, m] = sum_v <v|T_n(H~) A T_m(H~) B|v> (bdg_moment_matrix)
 // Part of the single translation unit bodge_hip.hip (included after apply.hpp): the kernels live in namespace
-// bdg, the driver in the unnamed namespace beside run_apply_series.
+// bdg, the driver in the unnamed namespace beside run_apply_series;
+// set-up and lanes by family_setup and the column rule of family.hpp.
 //
 // Two recurrences and a Gram product.  For a batch of start columns |r> in the planar batch
 // layout of apply.hpp (double2[4][nb][rl], one payload = one complex column in every arithmetic mode):
@@ -233,14 +234,9 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
     lanczos_free(sys);
     HIP_TRY(hipSetDevice(sys->device));
 
-    // Arithmetic mode and columns per batch as in run_apply_series.
+    // Arithmetic mode of the family, columns per batch by its column rule (family.hpp).
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const double per_column = (double)nb * 4 * 16.0;
-    int width = real ? 32 : 64;
-    while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
-    int rl = std::max(4, next_pow2(std::min(n_vectors, width)));
-    if (sys->lanes_override >= 4) rl = sys->lanes_override;
+    int rl = family_column_lanes(sys, mode, n_vectors);
 
     // Panels: Mb rows each, the largest multiple of 64 (or M itself) for which both stay within the budget.  A batch
     // that is too wide even for 64 rows is narrowed (down to 4 lanes) unless the lanes are fixed.
@@ -266,19 +262,11 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
     const int64_t n_slices = (K + slice - 1) / slice;
     if (n_slices > 65535) return fail(BDG_EINVAL, "BODGE_AMD_CORRELATION_SLICE = %d cuts a panel row into more than 65535 slices", slice);
 
-    FamilyPlan<ApplyKernels::Kernel> aplan;
-    if (int rc = make_family_plan<ApplyKernels>(sys, rl, mode, 0, &aplan)) return rc;
-    const StepPlan& plan = aplan.step;
-    const int rv = rl * mode.per_lane;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)K;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
+    // (the lanes are final only here, after the panels may have narrowed them)
+    FamilySetup<ApplyKernels> fs;
+    if (int rc = family_setup(sys, mode, rl, 0, &fs)) return rc;
+    const StepPlan& plan = fs.plan.step;
+    const size_t vec_count = fs.vec_count;  // = K
     const int n_batches = (n_vectors + rl - 1) / rl;
 
     // start batch (kept: the X recurrence restarts from it), the two vector pairs, the caller's vectors of a batch
@@ -320,7 +308,7 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
             const int col_base = bt * rl;
             const int n_active = std::min(rl, n_vectors - col_base);
             bdg::ApplyArgs ca{};
-            ca.s = base;
+            ca.s = fs.base;
             ca.x = d_start.ptr;
             ca.n_functions = 1;
             ca.col_base = 0;
@@ -331,9 +319,9 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
                 ca.s.cur = cur;
                 ca.s.prev = prev;
                 ca.s.coef = coef;
-                ca.s.reverse = alternate ? (parity & 1) : 0;
+                ca.s.reverse = fs.alternate ? (parity & 1) : 0;
                 ca.coef_row = d_coef.ptr + coef_row;
-                aplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ca);
+                fs.plan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ca);
                 std::swap(cur, prev);
                 ++launches;
             };
@@ -398,9 +386,9 @@ int run_moment_matrix(bdg_system* sys, double scale, int n_moments, const bdg_op
         HIP_TRY(hipEventElapsedTime(&window, events[events.size() - 2], events[events.size() - 1]));
         perf.window_ms = window;
         perf.kernel_ms = window;
-        perf.bytes_per_launch = apply_bytes(sys, rv, mode, plan.dictionary, 1);
+        perf.bytes_per_launch = apply_bytes(sys, fs.rv, mode, plan.dictionary, 1);
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
+        family_perf(sys, plan, fs.rv, fs.strip_rows, 1, &perf);
         perf.correlation = 1;
         sys->perf = perf;
         return BDG_OK;

@@ -1,5 +1,5 @@
-// family.hpp - what the Clenshaw-family kernels and drivers share (fermi.hpp, apply.hpp, correlation.hpp, green.hpp,
-// green_map.hpp, green_states.hpp).  Part of the single translation unit bodge_hip.hip (included after
+// family.hpp - what the Clenshaw-family kernels and drivers share (fermi.hpp, apply.hpp, correlation.hpp,
+// response_map.hpp, green.hpp, green_map.hpp, green_bonds.hpp, green_states.hpp).  Part of the single translation unit bodge_hip.hip (included after
 // recurrence.hpp, before fermi.hpp): the kernels live in namespace bdg, the host helpers in the unnamed namespace.
 //
 // Every kernel of the family is one recurrence step  nx = coef * (H cur) - prev  written over prev, plus a few lines
@@ -19,6 +19,11 @@
 // FamilyTail holds the empty hooks: a tail derives from it and names only the hooks it uses.  The hooks and the common
 // epilogue are inline device functions; the two tile loops themselves stay in the __global__ functions (moved into a
 // shared device function they cost 2 - 4 VGPRs and ComplexPHMode spilled: DESIGN.md §16).
+//
+// On the host: the dispatch and the launch plan of a family kernel, the two width rules
+// (family_column_lanes; family_unit_width / family_unit_lanes), FamilySetup / family_setup - what every one of the
+// eight drivers decides before its first launch - and run_family_rounds, the loop of fermi.hpp and apply.hpp, whose
+// batches run side by side on the handle's stream sets.  The Green drivers' loop is in green_driver.hpp.
 #pragma once
 
 namespace bdg {
@@ -488,6 +493,188 @@ void family_perf(const bdg_system* sys, const StepPlan& plan, int rv, int strip_
     perf->dict_skipped = sys->dict_skipped;
     perf->streams = streams;
     perf->groups_per_launch = 1;
+}
+
+// The width rules.  One vector buffer of a batch stays within 96 MB (batch_width's rule for the one-step kernels);
+// set_lanes_per_row fixes the lanes instead.
+constexpr double kFamilyBufferBytes = 96.0 * 1024 * 1024;
+
+// Lanes per row of a call whose columns are complex (apply, correlation, response_map, green_states):
+// a payload is one column, 16 B per entry.  The widest power of two within the 96 MB, at most 64 columns - 32 in real
+// arithmetic, whose kernels count a column as two of their 64 vectors - and no wider than the call's columns need.
+int family_column_lanes(const bdg_system* sys, const ModeInfo& mode, int64_t n_columns) {
+    const double per_column = (double)sys->nb * 4 * 16.0;
+    int width = mode.real ? 32 : 64;
+    while (width > 4 && width * per_column > kFamilyBufferBytes) width >>= 1;
+    const int rl = std::max(4, next_pow2((int)std::min<int64_t>(n_columns, width)));
+    return sys->lanes_override >= 4 ? sys->lanes_override : rl;
+}
+
+// A call with unit start vectors (fermi, the Green tables): the widest batch in vectors - a power of two up to 64, a
+// real vector being half a payload - and the lanes per row of a batch of at most `n_active_max` of them.
+int family_unit_width(const bdg_system* sys, const ModeInfo& mode) {
+    const double per_vector = (double)sys->nb * 4 * (mode.real ? 8.0 : 16.0);
+    int width = 64;
+    while (width > 8 && width * per_vector > kFamilyBufferBytes) width >>= 1;
+    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * mode.per_lane);
+    return width;
+}
+int family_unit_lanes(const bdg_system* sys, const ModeInfo& mode, int n_active_max) {
+    const int rl = std::max(4, next_pow2((n_active_max + mode.per_lane - 1) / mode.per_lane));
+    return sys->lanes_override >= 4 && sys->lanes_override * mode.per_lane >= n_active_max ? sys->lanes_override : rl;
+}
+
+// What a family call has decided before its first launch, given its mode and lanes per row.
+template <typename Kernels>
+struct FamilySetup {
+    FamilyPlan<typename Kernels::Kernel> plan;
+    ModeInfo mode{};
+    int rl = 0, rv = 0;        // lanes per row, vectors per launch
+    bdg::StepArgs base{};      // the matrix side of every launch's arguments
+    int strip_rows = 0;
+    size_t vec_count = 0;      // payloads of one vector buffer
+    bool alternate = false;    // the tiles' direction alternates from launch to launch
+};
+
+template <typename Kernels>
+int family_setup(bdg_system* sys, const ModeInfo& mode, int rl, size_t extra_lds, FamilySetup<Kernels>* fs) {
+    fs->mode = mode;
+    fs->rl = rl;
+    fs->rv = rl * mode.per_lane;
+    if (int rc = make_family_plan<Kernels>(sys, rl, mode, extra_lds, &fs->plan)) return rc;
+    const StepPlan& plan = fs->plan.step;
+    if (int rc = matrix_args(sys, plan, &fs->base)) return rc;
+    // A row of t_n is one 16-byte payload per lane and component, 64 rl bytes, in every mode: per vector that is
+    // (real ? 32 : 64) bytes, and rv = (real ? 2 : 1) rl vectors share the row.
+    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &fs->base.tile_order, &fs->strip_rows))
+        return rc;
+    fs->vec_count = (size_t)4 * sys->nb * rl;
+    const VectorHints hints = family_vector_hints(fs->vec_count);
+    fs->base.stream_vectors = hints.stream_vectors;
+    fs->alternate = hints.alternate;
+    return BDG_OK;
+}
+
+// Streams of a call whose batches run side by side (fermi, apply): two of the handle's stream sets while one launch
+// leaves the GPU part empty (the rule of run_recurrence for the one-step kernels), never more than it has batches;
+// BODGE_AMD_STREAMS overrides.
+int family_streams(const bdg_system* sys, int rv, int n_batches) {
+    int n_streams = (double)sys->nb * rv <= kSideBySideOneStepLimit ? 2 : 1;
+    if (const char* env = knob::raw("BODGE_AMD_STREAMS")) n_streams = std::clamp(atoi(env), 1, 4);
+    return std::max(1, std::min(n_streams, n_batches));
+}
+
+// What a feature of the rounds loop need not say.  A feature type has
+//   Args, kFlag, launch_bytes   the kernel's arguments (with n_active), the call's bdg_perf flag, its bytes_per_launch
+//   kVectors, kRecord      vector buffers of a stream set in use, 2 (vec_a, vec_b) .. 4; whether sys->perf takes the record
+//   upload(st)             reserve its device buffers, upload its tables
+//   start_batch(b, set, &args)   the batch's fields into args, its start kernels onto the set's stream; returns the
+//                          active columns, or an error (< 0)
+//   point(&args, k)        the source coefficient of T_k into args
+//   end_batch(b, set, y, args), drain_batch(b, set, args)   after the stop event; after the round's hipGetLastError
+//   finish(sets, st)       after the last round: joins the side streams before the handle's stream is awaited
+//   release()              its device buffers given back; called once, on every way out
+struct FamilyFeature {
+    static constexpr bool kRecord = true;  // (a feature whose caller decides hides it with a member: ApplySeries)
+    template <typename Args>
+    int drain_batch(int, StreamSet*, const Args&) { return BDG_OK; }
+};
+
+// The Clenshaw loop of fermi.hpp and apply.hpp: batches in rounds of one per stream; per batch b_M = b_{M+1} = 0, then
+// one launch per coefficient (k = M-1 .. 0), the batches of a round in turn so that their launches fill each other's gaps.
+template <typename Kernels, typename Feature>
+int run_family_rounds(bdg_system* sys, const FamilySetup<Kernels>& fs, double scale, int n_moments, int n_batches, Feature& f) {
+    const int n_streams = family_streams(sys, fs.rv, n_batches);
+    std::vector<StreamSet*> sets;
+    if (int rc = side_stream_sets(sys, n_streams, &sets)) return rc;
+    for (StreamSet* set : sets) {
+        DeviceBuffer<double2>* const vectors[4] = {&set->vec_a, &set->vec_b, &set->vec_c, &set->vec_d};
+        for (int v = 0; v < Feature::kVectors; ++v)
+            if (int rc = vectors[v]->reserve(fs.vec_count)) return rc;
+    }
+    const StepPlan& plan = fs.plan.step;
+    std::vector<hipEvent_t> events;
+    auto body = [&]() -> int {
+        hipStream_t st = sys->stream;
+        if (int rc = f.upload(st)) return rc;
+        // (tables, packed blocks and the feature's uploads are on the handle's stream: the side streams wait for them)
+        if (!sys->ev_side) HIP_TRY(hipEventCreateWithFlags(&sys->ev_side, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(sys->ev_side, st));
+        for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamWaitEvent(sets[(size_t)s]->stream, sys->ev_side, 0));
+        events.assign((size_t)2 * n_batches, nullptr);
+        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
+
+        const int fill_grid = (int)std::min<size_t>(4096, (fs.vec_count + 255) / 256);
+        bdg_perf perf{};
+        std::vector<typename Feature::Args> args((size_t)n_streams);
+        std::vector<double2*> cur((size_t)n_streams), prev((size_t)n_streams);
+        for (int first = 0; first < n_batches; first += n_streams) {
+            const int last = std::min(n_batches, first + n_streams);
+            for (int b = first; b < last; ++b) {
+                const size_t q = (size_t)(b - first);
+                StreamSet* set = sets[q];
+                args[q] = typename Feature::Args{};
+                args[q].s = fs.base;
+                cur[q] = set->vec_a.ptr;
+                prev[q] = set->vec_b.ptr;
+                if (int rc = f.start_batch(b, set, &args[q]); rc < 0) return rc;
+                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_a.ptr, (int64_t)fs.vec_count);
+                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_b.ptr, (int64_t)fs.vec_count);
+                HIP_TRY(hipEventRecord(events[(size_t)2 * b], set->stream));
+            }
+            for (int n = 0; n < n_moments; ++n) {
+                const int k = n_moments - 1 - n;
+                for (int b = first; b < last; ++b) {
+                    const size_t q = (size_t)(b - first);
+                    typename Feature::Args& ca = args[q];
+                    ca.s.cur = cur[q];
+                    ca.s.prev = prev[q];
+                    ca.s.coef = (k == 0 ? 1.0 : 2.0) / scale;
+                    ca.s.reverse = fs.alternate ? (n & 1) : 0;
+                    f.point(&ca, k);
+                    fs.plan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, sets[q]->stream>>>(ca);
+                    std::swap(cur[q], prev[q]);
+                }
+            }
+            for (int b = first; b < last; ++b) {
+                const size_t q = (size_t)(b - first);
+                HIP_TRY(hipEventRecord(events[(size_t)2 * b + 1], sets[q]->stream));
+                f.end_batch(b, sets[q], cur[q], args[q]);
+                perf.vector_steps += (int64_t)n_moments * args[q].n_active;
+            }
+            HIP_TRY(hipGetLastError());
+            for (int b = first; b < last; ++b)
+                if (int rc = f.drain_batch(b, sets[(size_t)(b - first)], args[(size_t)(b - first)])) return rc;
+        }
+        if (int rc = f.finish(sets, st)) return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        // kernel time: start to stop event of every batch; the window: the first start to the latest stop
+        float window = 0.f;
+        for (int b = 0; b < n_batches; ++b) {
+            float t = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t, events[(size_t)2 * b], events[(size_t)2 * b + 1]));
+            perf.kernel_ms += t;
+            HIP_TRY(hipEventElapsedTime(&t, events[0], events[(size_t)2 * b + 1]));
+            window = std::max(window, t);
+        }
+        perf.window_ms = window;
+        perf.launches = (int64_t)n_batches * n_moments;
+        perf.bytes_per_launch = f.launch_bytes;
+        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
+        family_perf(sys, plan, fs.rv, fs.strip_rows, n_streams, &perf);
+        perf.*Feature::kFlag = plan.dictionary ? 2 : 1;
+        if (f.kRecord) sys->perf = perf;
+        return BDG_OK;
+    };
+    const int rc = body();
+    if (rc) {  // (an error leaves nothing in flight: later calls reuse the streams' buffers)
+        (void)hipStreamSynchronize(sys->stream);
+        for (auto& side : sys->side_sets) (void)hipStreamSynchronize(side->stream);
+    }
+    for (hipEvent_t ev : events)
+        if (ev) (void)hipEventDestroy(ev);
+    f.release();
+    return rc;
 }
 
 }  // namespace

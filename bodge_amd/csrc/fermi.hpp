@@ -1,6 +1,7 @@
 // fermi.hpp - the local one-body density matrix f(H) on the Hamiltonian's block pattern (bdg_fermi_blocks)
 // Part of the single translation unit bodge_hip.hip (included after recurrence.hpp): the kernels live in
-// namespace bdg beside the recurrence kernels, the driver in the unnamed namespace beside run_recurrence.
+// namespace bdg beside the recurrence kernels, the driver in the unnamed namespace: its argument checks, its
+// colour tables and the feature FermiBlocks on the rounds loop of family.hpp (run_family_rounds).
 //
 // Probing + Clenshaw.  The sites are coloured so that two sites of one colour are far apart
 // in the graph of H; for colour c and Nambu component β the probe vector is r = Σ_{i ∈ c} e_{4i+β}, and
@@ -254,6 +255,73 @@ double clenshaw_bytes(const bdg_system* sys, int vectors, const ModeInfo& mode, 
     return algorithmic_bytes(sys, vectors, mode, dictionary) + 4.0 * (double)sys->nb;
 }
 
+// bdg_fermi_blocks on the rounds loop of family.hpp.  A batch is `colours_per_batch` whole colours; every batch
+// leaves its columns of the pattern blocks in d_out, which goes to the caller after the last one.
+struct FermiBlocks : FamilyFeature {
+    using Args = bdg::ClenshawArgs;
+    static constexpr int32_t bdg_perf::*kFlag = &bdg_perf::clenshaw;
+    static constexpr int kVectors = 2;
+    bdg_system* sys;
+    const FamilySetup<FermiKernels>& fs;
+    int n_colours, n_components, colours_per_batch;
+    const double* coef;
+    const int32_t* site_colour;
+    const std::vector<int64_t>& colour_ptr;  // per colour: its range of the entry list
+    const std::vector<int32_t>&ent_block, &ent_row, &ent_colour;
+    int64_t n_pat;
+    double* blocks_out;
+    double launch_bytes;
+    DeviceBuffer<int> d_colour, d_block, d_row, d_ent_colour;
+    DeviceBuffer<double2> d_out;
+
+    int upload(hipStream_t st) {
+        const int64_t nb = sys->nb;
+        if (int rc = d_colour.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
+        if (int rc = d_block.reserve(ent_block.size())) return rc;
+        if (int rc = d_row.reserve(ent_block.size())) return rc;
+        if (int rc = d_ent_colour.reserve(ent_block.size())) return rc;
+        if (int rc = d_out.reserve((size_t)std::max<int64_t>(1, n_pat) * 16)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_colour.ptr, site_colour, sizeof(int) * nb, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_block.ptr, ent_block.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_row.ptr, ent_row.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_ent_colour.ptr, ent_colour.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(d_out.ptr, 0, sizeof(double2) * 16 * (size_t)n_pat, st));
+        return BDG_OK;
+    }
+    int start_batch(int b, StreamSet*, Args* ca) {
+        ca->site_colour = d_colour.ptr;
+        ca->colour_base = b * colours_per_batch;
+        ca->comp_shift = n_components == 4 ? 2 : 1;
+        ca->n_active = std::min(colours_per_batch, n_colours - ca->colour_base) * n_components;
+        return ca->n_active;
+    }
+    void point(Args* ca, int k) { ca->source = coef[k]; }
+    void end_batch(int, StreamSet* set, const double2* y, const Args& ca) {
+        const int c0 = ca.colour_base, c1 = c0 + ca.n_active / n_components;
+        const int64_t e0 = colour_ptr[(size_t)c0], count = colour_ptr[(size_t)c1] - e0;
+        if (count > 0) {
+            const int64_t total = count * 4 * n_components;
+            const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
+            const auto extract = fs.mode.real ? bdg::fermi_extract<2> : bdg::fermi_extract<1>;
+            extract<<<grid, 256, 0, set->stream>>>(y, sys->nb, fs.rl, d_block.ptr + e0, d_row.ptr + e0, d_ent_colour.ptr + e0, count,
+                                                   c0, ca.comp_shift, d_out.ptr);
+        }
+    }
+    // the side streams join the handle's, which then carries d_out to the caller
+    int finish(const std::vector<StreamSet*>& sets, hipStream_t st) {
+        for (size_t s = 1; s < sets.size(); ++s) {
+            HIP_TRY(hipEventRecord(sys->ev_side, sets[s]->stream));
+            HIP_TRY(hipStreamWaitEvent(st, sys->ev_side, 0));
+        }
+        HIP_TRY(hipMemcpyAsync(blocks_out, d_out.ptr, sizeof(double2) * 16 * (size_t)n_pat, hipMemcpyDeviceToHost, st));
+        return BDG_OK;
+    }
+    void release() {
+        for (DeviceBuffer<int>* buf : {&d_colour, &d_block, &d_row, &d_ent_colour}) buf->release();
+        d_out.release();
+    }
+};
+
 int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double* coef, int n_colours,
                      const int32_t* site_colour, int n_components, const int32_t* pat_indptr,
                      const int32_t* pat_indices, double* blocks_out) {
@@ -298,168 +366,15 @@ int run_fermi_blocks(bdg_system* sys, double scale, int n_moments, const double*
             }
     }
 
-    // Arithmetic and storage mode as for a recurrence with real start vectors (the probes are 0 / 1).
+    // Arithmetic and storage mode as for a recurrence with real start vectors (the probes are 0 / 1).  Vectors per
+    // batch: whole colours, by the unit rule of family.hpp.
     const ModeInfo mode = family_mode(sys);
-    const bool real = mode.real;
-    const int per_lane = mode.per_lane;
-    // Vectors per batch: whole colours, the widest power of two up to 64 whose vector buffer stays within
-    // 96 MB (batch_width's rule); set_lanes_per_row fixes the lanes instead.
-    const double per_vector = (double)nb * 4 * (real ? 8.0 : 16.0);
-    int width = 64;
-    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
-    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * per_lane);
-    if (real && width > 64) width = 64;
-    const int colours_per_batch = std::max(1, std::min(n_colours, width / n_components));
-    const int n_active_max = colours_per_batch * n_components;
-    int rl = std::max(4, next_pow2((n_active_max + per_lane - 1) / per_lane));
-    if (sys->lanes_override >= 4 && sys->lanes_override * per_lane >= n_active_max) rl = sys->lanes_override;
-    const int rv = rl * per_lane;
-    FamilyPlan<FermiKernels::Kernel> cplan;
-    if (int rc = make_family_plan<FermiKernels>(sys, rl, mode, 0, &cplan)) return rc;
-    const StepPlan& plan = cplan.step;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, (real ? 32.0 : 64.0) * rv, &base.tile_order,
-                                    &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
-    const int n_batches = (n_colours + colours_per_batch - 1) / colours_per_batch;
-
-    // Side by side on two of the handle's stream sets while one launch leaves the GPU part empty (the rule of
-    // run_recurrence for the one-step kernels); BODGE_AMD_STREAMS overrides.
-    int n_streams = (double)nb * rv <= kSideBySideOneStepLimit ? 2 : 1;
-    if (const char* env = knob::raw("BODGE_AMD_STREAMS")) n_streams = std::clamp(atoi(env), 1, 4);
-    n_streams = std::max(1, std::min(n_streams, n_batches));
-    while ((int)sys->side_sets.size() < n_streams - 1) {
-        auto side = std::make_unique<StreamSet>();
-        if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
-        sys->side_sets.push_back(std::move(side));
-    }
-    std::vector<StreamSet*> sets{sys};
-    for (int s = 1; s < n_streams; ++s) sets.push_back(sys->side_sets[(size_t)s - 1].get());
-    for (StreamSet* set : sets) {
-        if (int rc = set->vec_a.reserve(vec_count)) return rc;
-        if (int rc = set->vec_b.reserve(vec_count)) return rc;
-    }
-
-    DeviceBuffer<int> d_colour, d_block, d_row, d_ent_colour;
-    DeviceBuffer<double2> d_out;
-    std::vector<hipEvent_t> events;
-    auto body = [&]() -> int {
-        if (int rc = d_colour.reserve((size_t)std::max<int64_t>(1, nb))) return rc;
-        if (int rc = d_block.reserve(ent_block.size())) return rc;
-        if (int rc = d_row.reserve(ent_block.size())) return rc;
-        if (int rc = d_ent_colour.reserve(ent_block.size())) return rc;
-        if (int rc = d_out.reserve((size_t)std::max<int64_t>(1, n_pat) * 16)) return rc;
-        hipStream_t st = sys->stream;
-        HIP_TRY(hipMemcpyAsync(d_colour.ptr, site_colour, sizeof(int) * nb, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_block.ptr, ent_block.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_row.ptr, ent_row.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_ent_colour.ptr, ent_colour.data(), sizeof(int) * ent_block.size(), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(d_out.ptr, 0, sizeof(double2) * 16 * (size_t)n_pat, st));
-        // (tables, packed blocks and the uploads above are on the handle's stream: the side streams wait for them)
-        if (!sys->ev_side) HIP_TRY(hipEventCreateWithFlags(&sys->ev_side, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(sys->ev_side, st));
-        for (int s = 1; s < n_streams; ++s) HIP_TRY(hipStreamWaitEvent(sets[(size_t)s]->stream, sys->ev_side, 0));
-        events.assign((size_t)2 * n_batches, nullptr);
-        for (auto& ev : events) HIP_TRY(hipEventCreate(&ev));
-
-        const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
-        bdg_perf perf{};
-        for (int first = 0; first < n_batches; first += n_streams) {
-            const int last = std::min(n_batches, first + n_streams);
-            std::vector<bdg::ClenshawArgs> args((size_t)(last - first));
-            std::vector<double2*> cur((size_t)(last - first)), prev((size_t)(last - first));
-            for (int b = first; b < last; ++b) {
-                StreamSet* set = sets[(size_t)(b - first)];
-                bdg::ClenshawArgs& ca = args[(size_t)(b - first)];
-                ca.s = base;
-                ca.site_colour = d_colour.ptr;
-                ca.colour_base = b * colours_per_batch;
-                ca.comp_shift = n_components == 4 ? 2 : 1;
-                ca.n_active = std::min(colours_per_batch, n_colours - ca.colour_base) * n_components;
-                cur[(size_t)(b - first)] = set->vec_a.ptr;
-                prev[(size_t)(b - first)] = set->vec_b.ptr;
-                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_a.ptr, (int64_t)vec_count);
-                bdg::fill_zero<<<fill_grid, 256, 0, set->stream>>>(set->vec_b.ptr, (int64_t)vec_count);
-                HIP_TRY(hipEventRecord(events[(size_t)2 * b], set->stream));
-            }
-            // b_k for k = M-1 .. 1, then y: one launch per coefficient, the batches of the round in turn
-            for (int n = 0; n < n_moments; ++n) {
-                const int k = n_moments - 1 - n;
-                for (int b = first; b < last; ++b) {
-                    const size_t q = (size_t)(b - first);
-                    bdg::ClenshawArgs& ca = args[q];
-                    ca.s.cur = cur[q];
-                    ca.s.prev = prev[q];
-                    ca.s.coef = (k == 0 ? 1.0 : 2.0) / scale;
-                    ca.s.reverse = alternate ? (n & 1) : 0;
-                    ca.source = coef[k];
-                    cplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, sets[q]->stream>>>(ca);
-                    std::swap(cur[q], prev[q]);
-                }
-            }
-            for (int b = first; b < last; ++b) {
-                const size_t q = (size_t)(b - first);
-                HIP_TRY(hipEventRecord(events[(size_t)2 * b + 1], sets[q]->stream));
-                const int c0 = args[q].colour_base, c1 = c0 + args[q].n_active / n_components;
-                const int64_t e0 = colour_ptr[(size_t)c0], count = colour_ptr[(size_t)c1] - e0;
-                if (count > 0) {
-                    const int64_t total = count * 4 * n_components;
-                    const int grid = (int)std::min<int64_t>(8192, (total + 255) / 256);
-                    if (real)
-                        bdg::fermi_extract<2><<<grid, 256, 0, sets[q]->stream>>>(
-                            cur[q], nb, rl, d_block.ptr + e0, d_row.ptr + e0, d_ent_colour.ptr + e0, count, c0,
-                            args[q].comp_shift, d_out.ptr);
-                    else
-                        bdg::fermi_extract<1><<<grid, 256, 0, sets[q]->stream>>>(
-                            cur[q], nb, rl, d_block.ptr + e0, d_row.ptr + e0, d_ent_colour.ptr + e0, count, c0,
-                            args[q].comp_shift, d_out.ptr);
-                }
-                perf.vector_steps += (int64_t)n_moments * args[q].n_active;
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        for (int s = 1; s < n_streams; ++s) {
-            HIP_TRY(hipEventRecord(sys->ev_side, sets[(size_t)s]->stream));
-            HIP_TRY(hipStreamWaitEvent(st, sys->ev_side, 0));
-        }
-        HIP_TRY(hipMemcpyAsync(blocks_out, d_out.ptr, sizeof(double2) * 16 * (size_t)n_pat, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        float window = 0.f;
-        for (int b = 0; b < n_batches; ++b) {
-            float t = 0.f;
-            HIP_TRY(hipEventElapsedTime(&t, events[(size_t)2 * b], events[(size_t)2 * b + 1]));
-            perf.kernel_ms += t;
-            HIP_TRY(hipEventElapsedTime(&t, events[0], events[(size_t)2 * b + 1]));
-            window = std::max(window, t);
-        }
-        perf.window_ms = window;
-        perf.launches = (int64_t)n_batches * n_moments;
-        perf.bytes_per_launch = clenshaw_bytes(sys, rv, mode, plan.dictionary);
-        perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, n_streams, &perf);
-        perf.clenshaw = plan.dictionary ? 2 : 1;
-        sys->perf = perf;
-        return BDG_OK;
-    };
-    const int rc = body();
-    if (rc) {
-        (void)hipStreamSynchronize(sys->stream);
-        for (auto& side : sys->side_sets) (void)hipStreamSynchronize(side->stream);
-    }
-    for (hipEvent_t ev : events)
-        if (ev) (void)hipEventDestroy(ev);
-    d_colour.release();
-    d_block.release();
-    d_row.release();
-    d_ent_colour.release();
-    d_out.release();
-    return rc;
+    const int colours_per_batch = std::max(1, std::min(n_colours, family_unit_width(sys, mode) / n_components));
+    FamilySetup<FermiKernels> fs;
+    if (int rc = family_setup(sys, mode, family_unit_lanes(sys, mode, colours_per_batch * n_components), 0, &fs)) return rc;
+    FermiBlocks feature{{}, sys, fs, n_colours, n_components, colours_per_batch, coef, site_colour, colour_ptr, ent_block, ent_row,
+                        ent_colour, n_pat, blocks_out, clenshaw_bytes(sys, fs.rv, mode, fs.plan.step.dictionary)};
+    return run_family_rounds(sys, fs, scale, n_moments, (n_colours + colours_per_batch - 1) / colours_per_batch, feature);
 }
 
 }  // namespace

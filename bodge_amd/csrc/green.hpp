@@ -163,7 +163,7 @@ int run_green_moments(bdg_system* sys, double scale, int n_moments, int n_source
     const ModeInfo mode = family_mode(sys);
     const GreenWidth lanes = green_unit_width(sys, mode, n_sources);
     GreenSetup<GreenKernels> gs;
-    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
+    if (int rc = family_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
     const size_t moment_bytes = (size_t)n_targets * 4 * (size_t)lanes.width * sizeof(double2);  // one moment of a full batch
     green_cut_ranges(n_moments, moment_bytes, &gs);
     GreenPicked feature{{}, sys, gs, lanes.width, n_sources, n_targets, source_rows, target_block_rows, slot_of,

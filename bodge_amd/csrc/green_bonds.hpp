@@ -304,7 +304,7 @@ int run_green_bond_blocks(bdg_system* sys, double scale, int n_moments, int n_we
     const int batch_sites = lanes.width / n_components;
     const int n_batches = (n_sites + batch_sites - 1) / batch_sites;
     GreenSetup<GreenBondKernels> gs;
-    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
+    if (int rc = family_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
 
     // The pattern's blocks by batch: a block belongs to the batch of its column site and has an index in that batch's
     // table; batch_blocks lists the blocks of batch b (pattern order) from batch_ptr[b] on.

@@ -6,7 +6,7 @@
 // All four walk batches of start vectors x ranges of moments x moments on the handle's stream: a
 // batch's vectors run t_{n+1} = 2 H~ t_n - t_{n-1}, every launch leaves its moment in a slice of a device table, and
 // when a range of moments is full the feature hands the table on.  GreenSetup is what such a call decides before its
-// first launch, run_green_ranges the loop; a driver keeps its argument checks, its host-side index tables and a
+// first launch (the family's set-up of family.hpp plus the ranges), run_green_ranges the loop; a driver keeps its argument checks, its host-side index tables and a
 // feature type whose hooks the loop calls (resolved at compile time: a launch of a small lattice is 6 - 7 us, and host
 // time per launch shows).
 #pragma once
@@ -15,55 +15,23 @@ namespace {
 
 constexpr size_t kGreenTableBytes = (size_t)256 << 20;  // device moment table: a range of moments at a time
 
-// Vectors per batch and lanes per row of a call with unit start vectors: the widest power of two up to 64 whose vector
-// buffer stays within 96 MB (batch_width's rule for the one-step kernels), at most the `n_vectors` the call has;
-// set_lanes_per_row fixes the lanes instead.
+// Vectors per batch and lanes per row of a call with unit start vectors: the unit rule of family.hpp, at most the
+// `n_vectors` the call has.
 struct GreenWidth {
     int width, rl;
 };
 GreenWidth green_unit_width(const bdg_system* sys, const ModeInfo& mode, int n_vectors) {
-    const double per_vector = (double)sys->nb * 4 * (mode.real ? 8.0 : 16.0);
-    int width = 64;
-    while (width > 8 && width * per_vector > 96.0 * 1024 * 1024) width >>= 1;
-    if (sys->lanes_override >= 4) width = std::min(64, sys->lanes_override * mode.per_lane);
-    width = std::min(width, n_vectors);
-    int rl = std::max(4, next_pow2((width + mode.per_lane - 1) / mode.per_lane));
-    if (sys->lanes_override >= 4 && sys->lanes_override * mode.per_lane >= width) rl = sys->lanes_override;
-    return {width, rl};
+    const int width = std::min(family_unit_width(sys, mode), n_vectors);
+    return {width, family_unit_lanes(sys, mode, width)};
 }
 
-// What a call has decided before its first launch.  green_setup fills everything but the ranges, which need the
-// bytes of one moment's table - and those follow from the lanes and, for the partials of green_states.hpp, from the
-// grid: green_cut_ranges.
+// What a call has decided before its first launch: the family's set-up (family_setup fills it) and the ranges, which
+// need the bytes of one moment's table - and those follow from the lanes and, for the partials of green_states.hpp,
+// from the grid: green_cut_ranges.
 template <typename Kernels>
-struct GreenSetup {
-    FamilyPlan<typename Kernels::Kernel> plan;
-    ModeInfo mode{};
-    int rl = 0, rv = 0;        // lanes per row, vectors per launch
-    bdg::StepArgs base{};      // the matrix side of every launch's arguments
-    int strip_rows = 0;
-    size_t vec_count = 0;      // payloads of one vector buffer
-    bool alternate = false;    // the tiles' direction alternates from launch to launch
+struct GreenSetup : FamilySetup<Kernels> {
     int range = 0, n_ranges = 0;  // moments per fill of the device table, fills per batch
 };
-
-template <typename Kernels>
-int green_setup(bdg_system* sys, const ModeInfo& mode, int rl, size_t extra_lds, GreenSetup<Kernels>* gs) {
-    gs->mode = mode;
-    gs->rl = rl;
-    gs->rv = rl * mode.per_lane;
-    if (int rc = make_family_plan<Kernels>(sys, rl, mode, extra_lds, &gs->plan)) return rc;
-    const StepPlan& plan = gs->plan.step;
-    if (int rc = matrix_args(sys, plan, &gs->base)) return rc;
-    // (a row of t_n: one 16-byte payload per lane and component, (real ? 32 : 64) bytes per vector)
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &gs->base.tile_order, &gs->strip_rows))
-        return rc;
-    gs->vec_count = (size_t)4 * sys->nb * rl;
-    const VectorHints hints = family_vector_hints(gs->vec_count);
-    gs->base.stream_vectors = hints.stream_vectors;
-    gs->alternate = hints.alternate;
-    return BDG_OK;
-}
 
 // A range of moments whose tables (`moment_bytes` each, the widest batch's) fit BODGE_AMD_GREEN_TABLE_BYTES.
 template <typename Kernels>

@@ -174,7 +174,7 @@ int run_green_local_moments(bdg_system* sys, double scale, int n_moments, int n_
     const GreenWidth lanes = green_unit_width(sys, mode, n_sites * n_components);
     const int batch_sites = lanes.width / n_components;
     GreenSetup<GreenLocalKernels> gs;
-    if (int rc = green_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
+    if (int rc = family_setup(sys, mode, lanes.rl, 0, &gs)) return rc;
     const size_t moment_bytes = (size_t)batch_sites * 4 * n_components * sizeof(double2);  // one moment of a full batch
     green_cut_ranges(n_moments, moment_bytes, &gs);
     GreenLocal feature{{}, sys, gs, batch_sites, n_sites, n_components, block_rows, position, start_rows,

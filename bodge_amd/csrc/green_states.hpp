@@ -311,17 +311,11 @@ int run_green_state_moments(bdg_system* sys, double scale, int n_moments, int n_
     // Arithmetic as for apply(): real whenever the matrix is real, the columns complex all the same (Re and Im in
     // the two slots of a payload).  In every mode a payload is one column, so `rl` lanes carry rl columns.
     const ModeInfo mode = family_mode(sys);
-    // Columns per batch by the width rule of run_apply_series: the widest power of two whose vector buffer stays
-    // within 96 MB, at most 64 columns - 32 in real arithmetic; set_lanes_per_row fixes the lanes instead.  A batch
-    // holds whole states.
-    const double per_column = (double)nb * 4 * 16.0;
-    int width = mode.real ? 32 : 64;
-    while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
-    int rl = std::max(4, next_pow2((int)std::min<int64_t>((int64_t)n_states * n_components, width)));
-    if (sys->lanes_override >= 4) rl = sys->lanes_override;
+    // Columns per batch by the column rule of family.hpp.  A batch holds whole states.
+    const int rl = family_column_lanes(sys, mode, (int64_t)n_states * n_components);
     const int batch_states = rl / n_components;
     GreenSetup<GreenStateKernels> gs;
-    if (int rc = green_setup(sys, mode, rl, bdg::GreenStateTail::kExtraLds, &gs)) return rc;
+    if (int rc = family_setup(sys, mode, rl, bdg::GreenStateTail::kExtraLds, &gs)) return rc;
     const GreenProjectKernel project = green_state_project_for(rl);
     if (!project) return fail(BDG_EINVAL, "unsupported lanes-per-row %d for the projected recurrence kernels", rl);
 

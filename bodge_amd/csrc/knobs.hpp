@@ -64,7 +64,7 @@
 //                                            fills and copies out one range of moments after the other (tests lower it)
 //   bdg_green_bond_blocks (green_bonds.hpp) follows the same switches and the same limit: a range of moments is contracted
 //   into the result on the device when the table is full, whatever the ranges the bits are the same
-//   bdg_green_state_moments (green_states.hpp) follows the same switches (its width rule is that of bdg_apply_series); the
+//   bdg_green_state_moments (green_states.hpp) follows the same switches (its width rule is the column rule of family.hpp, as for bdg_apply_series); the
 //   workgroups' partials of a range of moments count towards BODGE_AMD_GREEN_TABLE_BYTES with the table
 //   bdg_moment_matrix (correlation.hpp) follows DICT, REAL, PH, STREAM_VECTORS, ALTERNATE, BLOCKS_PER_CU and L2_BUDGET as
 //   bdg_apply_series does (bdg_set_lanes_per_row fixes its batch width), and

@@ -78,11 +78,7 @@ struct Batch {
         HIP_TRY(hipSetDevice(sys->device));
         ss = sys;
         if (set_index > 0) {
-            while ((int)sys->side_sets.size() < set_index) {
-                auto side = std::make_unique<StreamSet>();
-                if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
-                sys->side_sets.push_back(std::move(side));
-            }
+            if (int rc = side_stream_sets(sys, set_index + 1, nullptr)) return rc;
             ss = sys->side_sets[(size_t)set_index - 1].get();
         }
         // Real arithmetic applies when H has no imaginary part and the start vectors are real
@@ -985,11 +981,7 @@ int run_recurrence_once(bdg_system* sys, double scale, int n_steps, int n_vector
         const bool have = (int)sys->side_sets.size() >= n_streams - 1 && sys->side_sets[0]->vec_a.count > 0;
         if (!have && (double)free_bytes < 1.25 * (n_streams - 1) * 4.0 * 256.0 * (double)sys->ncols + (64 << 20)) n_streams = 1;
     }
-    while ((int)sys->side_sets.size() < n_streams - 1) {
-        auto side = std::make_unique<StreamSet>();
-        if (int rc = pooled_stream(sys->device, (int)sys->side_sets.size(), &side->stream)) return fail(rc, "stream creation failed");
-        sys->side_sets.push_back(std::move(side));
-    }
+    if (int rc = side_stream_sets(sys, n_streams, nullptr)) return rc;
     if (!sys->ev_side) HIP_TRY(hipEventCreateWithFlags(&sys->ev_side, hipEventDisableTiming));
     std::vector<Batch> queued((size_t)n_batches);
     size_t stride0 = 0;

@@ -2,7 +2,7 @@
 //     K_{q,j}[g, d] = sum_nm c_q[n][m] sum_ab A[a, b] conj(X_m[(j, g), b]) X_n[(j, d), a],   X_n = T_n(H~) E
 // for the unit columns E on the support of A (bdg_response_map).  Part of the single translation unit bodge_hip.hip
 // (included after correlation.hpp): the kernels live in namespace bdg, the driver in the unnamed namespace beside
-// run_moment_matrix.
+// run_moment_matrix (correlation.hpp).
 //
 // One recurrence of S <= 32 columns, one dense product, one contraction.  The columns advance through
 // the stored-source Clenshaw kernels of apply.hpp with a zero coefficient (a plain step 2 H~ t_n - t_{n-1}), as in
@@ -194,13 +194,9 @@ int run_response_map(bdg_system* sys, double scale, int n_moments, int n_source_
     subspace_free(sys);
     HIP_TRY(hipSetDevice(sys->device));
 
-    // Arithmetic mode and lanes as in run_moment_matrix; the S columns fill whole batches of rl lanes.
+    // Arithmetic mode of the family, lanes by its column rule (family.hpp); the S columns fill whole batches of rl lanes.
     const ModeInfo mode = family_mode(sys);
-    const double per_column = (double)nb * 4 * 16.0;
-    int width = mode.real ? 32 : 64;
-    while (width > 4 && width * per_column > 96.0 * 1024 * 1024) width >>= 1;
-    int rl = std::max(4, next_pow2(std::min(n_source_rows, width)));
-    if (sys->lanes_override >= 4) rl = sys->lanes_override;
+    const int rl = family_column_lanes(sys, mode, n_source_rows);
     const int n_batches = (n_source_rows + rl - 1) / rl;
     const int Sp = n_batches * rl;  // padded columns of a site's entries in a panel row
     const int M = n_moments;
@@ -224,19 +220,10 @@ int run_response_map(bdg_system* sys, double scale, int n_moments, int n_source_
     if ((K_max + bdg::kRespTile - 1) / bdg::kRespTile > 0x7fffffffLL)
         return fail(BDG_EINVAL, "bdg_response_map: a chunk of %d sites is too wide for one launch", chunk);
 
-    FamilyPlan<ApplyKernels::Kernel> aplan;
-    if (int rc = make_family_plan<ApplyKernels>(sys, rl, mode, 0, &aplan)) return rc;
-    const StepPlan& plan = aplan.step;
-    const int rv = rl * mode.per_lane;
-    bdg::StepArgs base{};
-    if (int rc = matrix_args(sys, plan, &base)) return rc;
-    int strip_rows = 0;
-    if (int rc = prepare_tile_order(sys, plan.rows_per_tile, plan.n_tiles, 64.0 * rl, &base.tile_order, &strip_rows))
-        return rc;
-    const size_t vec_count = (size_t)4 * nb * rl;
-    const VectorHints hints = family_vector_hints(vec_count);
-    base.stream_vectors = hints.stream_vectors;
-    const bool alternate = hints.alternate;
+    FamilySetup<ApplyKernels> fs;
+    if (int rc = family_setup(sys, mode, rl, 0, &fs)) return rc;
+    const StepPlan& plan = fs.plan.step;
+    const size_t vec_count = fs.vec_count;
 
     DeviceBuffer<double2> d_start, d_xa, d_xb, d_xpanel, d_zpanel, d_coef, d_a, d_out, d_zero;
     DeviceBuffer<int64_t> d_rows;
@@ -281,7 +268,7 @@ int run_response_map(bdg_system* sys, double scale, int n_moments, int n_source_
                 HIP_TRY(hipMemcpyAsync(cur, d_start.ptr, sizeof(double2) * vec_count, hipMemcpyDeviceToDevice, st));
                 bdg::fill_zero<<<fill_grid, 256, 0, st>>>(prev, (int64_t)vec_count);
                 bdg::ApplyArgs ca{};
-                ca.s = base;
+                ca.s = fs.base;
                 ca.x = d_start.ptr;
                 ca.n_functions = 1;
                 ca.col_base = 0;
@@ -293,8 +280,8 @@ int run_response_map(bdg_system* sys, double scale, int n_moments, int n_source_
                         ca.s.cur = cur;
                         ca.s.prev = prev;
                         ca.s.coef = (n == 1 ? 1.0 : 2.0) / scale;
-                        ca.s.reverse = alternate ? (n & 1) : 0;
-                        aplan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ca);
+                        ca.s.reverse = fs.alternate ? (n & 1) : 0;
+                        fs.plan.kernel<<<plan.grid, bdg::kBlockThreads, plan.lds_bytes, st>>>(ca);
                         std::swap(cur, prev);
                         ++launches;
                     }
@@ -330,9 +317,9 @@ int run_response_map(bdg_system* sys, double scale, int n_moments, int n_source_
         HIP_TRY(hipEventElapsedTime(&window, events[events.size() - 2], events[events.size() - 1]));
         perf.window_ms = window;
         perf.kernel_ms = window;
-        perf.bytes_per_launch = apply_bytes(sys, rv, mode, plan.dictionary, 1);
+        perf.bytes_per_launch = apply_bytes(sys, fs.rv, mode, plan.dictionary, 1);
         perf.bytes_moved = perf.bytes_per_launch * (double)perf.launches;
-        family_perf(sys, plan, rv, strip_rows, 1, &perf);
+        family_perf(sys, plan, fs.rv, fs.strip_rows, 1, &perf);
         perf.response_map = 1;
         sys->perf = perf;
         return BDG_OK;
