@@ -60,6 +60,7 @@ class Perf(C.Structure):
         ("green_states", C.c_int32),
         ("green_bonds", C.c_int32),
         ("roll_chunk", C.c_int32),
+        ("composed", C.c_int32),
         ("response_map", C.c_int32),
         ("gemm_ms", C.c_double),
         ("gemm_flops", C.c_double),
@@ -148,6 +149,7 @@ SIGNATURES = {
     "bdg_host_scan_blocks": (C.c_int, [_f64p, _i32p, C.c_int64, _u8p, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "bdg_host_compact_blocks": (C.c_int, [_f64p, _i32p, _i32p, C.c_int64, _u8p, _f64p, _i32p, _i32p]),
+    "bdg_host_composed_dots": (C.c_int, [C.c_int32, C.c_int32, _f64p, C.c_int64, _f64p, _f64p, C.c_int64]),
     "bdg_comm_init": (C.c_int, [C.c_int, _u8p, C.c_int32, C.c_int32, C.POINTER(_handle)]),
     "bdg_comm_info": (C.c_int, [_handle, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p]),
     "bdg_comm_allreduce_sum": (C.c_int, [_handle, _f64p, C.c_int64]),

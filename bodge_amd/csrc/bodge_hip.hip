@@ -55,6 +55,7 @@
 
 #include "knobs.hpp"
 #include "host_assembly.hpp"
+#include "composed.hpp"
 #include "kernels.hpp"
 #include "sweep.hpp"
 #include "twostage.hpp"
@@ -1021,6 +1022,16 @@ int bdg_host_compact_blocks(const double* data, const int32_t* indices, const in
     for (int64_t k = 0; k < indptr[nb]; ++k) kept += keep[k] ? 1 : 0;
     if (kept > 0 && (!data_out || !indices_out)) return fail(BDG_EINVAL, "null output");
     bdg_host::compact_blocks(data, indices, indptr, nb, keep, data_out, indices_out, indptr_out);
+    return BDG_OK;
+}
+
+int bdg_host_composed_dots(int32_t n_steps, int32_t n_vectors, const double* raw, int64_t raw_stride, double* d_out,
+                           double* e_out, int64_t ld) {
+    if (n_steps < 1 || n_vectors < 1) return fail(BDG_EINVAL, "n_steps and n_vectors must be >= 1");
+    if (!raw || !d_out || !e_out) return fail(BDG_EINVAL, "null argument");
+    if (raw_stride < 2 * (int64_t)n_vectors || ld < n_vectors) return fail(BDG_EINVAL, "raw_stride must be >= 2 * n_vectors and ld >= n_vectors");
+    for (int32_t r = 0; r < n_vectors; ++r)
+        bdg_host::composed_dots_vector(n_steps, raw + 2 * r, (size_t)raw_stride, d_out + r, e_out + r, (size_t)ld);
     return BDG_OK;
 }
 

@@ -19,6 +19,11 @@
 //                                            (default: shared between the lane groups side by side, as for the dictionary forms)
 //     BODGE_AMD_ROLL_CHUNKS=0                3-D rolling kernel: whole-column segments as units instead of runs of equal length
 //     BODGE_AMD_SWEEP_GEN=0                  write the random start block with the fill kernel instead of making it in the first sweep
+//     BODGE_AMD_SWEEP_COMPOSED=0|1           random-start runs that take cheb_sweep3 with one launch per sweep: classic sweeps (four array passes per
+//                                            three steps) / composed ones (cheb_sweep3_composed: step by T_3, three passes, dot products turned
+//                                            back on the host - composed.hpp).  1 has no effect where the route does not apply: unit starts,
+//                                            slabs, streamed forms, full 16-entry blocks (PH=0), any run with BODGE_AMD_MARCH set (0 included:
+//                                            its arms compare launch structures of the classic body).  Default: recurrence.hpp kComposedDefault
 //     BODGE_AMD_MARCH=1|2|3                  cheb_march3 for the three-step sweeps of random-start runs (default 0: one cheb_sweep3 launch per
 //                                            sweep and lane group).  1 = all sweeps of a 63-step chunk in one launch, tasks claimed by ticket,
 //                                            flags between neighbouring units; 3 = the same with a fixed unit per wave (needs the grid

@@ -467,6 +467,26 @@ SweepKernel sweep3_gen_kernel(const ModeInfo& mode, int lanes) {
     return sweep3_gen_kernel_for<ComplexMode>(lanes);
 }
 
+// cheb_sweep3_composed (sweep.hpp "K7b, composed"): dictionary forms of the particle-hole modes, 2 or 4 lanes per site;
+// nullptr = the form does not exist and the batch takes the classic sweep
+template <typename Mode>
+SweepKernel sweep3_composed_kernel_for(int lanes, bool reverse, bool gen) {
+    switch (lanes) {
+        case 2: return gen ? bdg::cheb_sweep3_composed<Mode, 2, false, true>
+                           : reverse ? bdg::cheb_sweep3_composed<Mode, 2, true> : bdg::cheb_sweep3_composed<Mode, 2, false>;
+        case 4: return gen ? bdg::cheb_sweep3_composed<Mode, 4, false, true>
+                           : reverse ? bdg::cheb_sweep3_composed<Mode, 4, true> : bdg::cheb_sweep3_composed<Mode, 4, false>;
+    }
+    return nullptr;
+}
+SweepKernel sweep3_composed_kernel(const ModeInfo& mode, int lanes, bool reverse, bool gen) {
+    switch (mode.id) {
+        case 2: return sweep3_composed_kernel_for<ComplexPHMode>(lanes, reverse, gen);
+        case 3: return sweep3_composed_kernel_for<RealPHMode>(lanes, reverse, gen);
+    }
+    return nullptr;
+}
+
 // cheb_sweep3 with streamed on-site blocks (particle-hole modes); `bonds`: the bond blocks as well.  The forms built:
 //   on-site records, real:     4 lanes x 4 waves (two workgroups per CU), 2 lanes x 4 waves (two per CU while the bond table
 //                              is small) and 2 lanes x 7 waves (one per CU)
@@ -563,7 +583,9 @@ struct SweepPlan {
     int depth = 2;  // recurrence steps per sweep: 2 (cheb_sweep) or 3 (cheb_sweep3)
     SweepKernel kernel = nullptr, kernel_reverse = nullptr;
     SweepKernel kernel_gen = nullptr;  // depth 3: first sweep of a random-start run, t_0 made in registers
-    MarchKernel march = nullptr;       // depth 3: all sweeps of a reduction chunk in one launch (nullptr = not available)
+    // depth 3, dictionary forms of the particle-hole modes: the composed sweep (nullptr = the form does not exist)
+    SweepKernel composed = nullptr, composed_reverse = nullptr, composed_gen = nullptr;
+    MarchKernel march = nullptr;      // depth 3: all sweeps of a reduction chunk in one launch (nullptr = not available)
     int march_grid = 0;                // workgroups of such a launch
     int grid = 0;
     int wg_waves = bdg::kSweepWaves;   // waves per workgroup (the streamed forms with one workgroup per CU: 7)
@@ -717,8 +739,14 @@ int make_sweep_plan(bdg_system* sys, const ModeInfo& mode, int lanes, int depth,
     } else {
         plan->lds_bytes = table + (size_t)bdg::kSweepWaves * depth * bdg::kWave * 4 * sizeof(double2);
     }
+    plan->composed = plan->composed_reverse = plan->composed_gen = nullptr;
+    if (depth == 3 && !streamed) {
+        plan->composed = sweep3_composed_kernel(mode, lanes, false, false);
+        plan->composed_reverse = sweep3_composed_kernel(mode, lanes, true, false);
+        plan->composed_gen = sweep3_composed_kernel(mode, lanes, false, true);
+    }
     if (plan->lds_bytes > 64 * 1024)
-        for (SweepKernel k : {plan->kernel, plan->kernel_reverse, plan->kernel_gen})
+        for (SweepKernel k : {plan->kernel, plan->kernel_reverse, plan->kernel_gen, plan->composed, plan->composed_reverse, plan->composed_gen})
             if (k) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (int)plan->lds_bytes));
     // one launch per chunk: the write-through stores address a buffer through a 32-bit byte offset

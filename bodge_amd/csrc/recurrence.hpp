@@ -11,6 +11,9 @@ namespace {
 //   begin()  choose kernel + mode, allocate, write t_0 (own rows) and zero t_{-1}
 //   step(n)  one launch of K1 (after the caller has refreshed the halo of t_n)
 //   finish() reduce partials (done per chunk inside step), copy dots to the host
+// Whether random-start runs take the composed three-step sweep where they can (BODGE_AMD_SWEEP_COMPOSED overrides): decided
+// by the interleaved measurement in DESIGN.md §4.
+constexpr bool kComposedDefault = true;
 constexpr int kMarchAborted = -77;  // (internal: a persistent launch gave up waiting - run_recurrence repeats the call sweep by sweep)
 
 struct Batch {
@@ -39,6 +42,10 @@ struct Batch {
     // two-steps-per-sweep form
     bool sweep = false, roll = false;
     bool gen_start = false;  // the first sweep makes the random start block itself (no fill kernel)
+    // Composed three-step sweeps (sweep.hpp "K7b, composed"): every launch steps by T_3 - reads u_k = t_{3k}, updates u_{k-1} to
+    // u_{k+1} in place - and the dot table holds the products of the levels inside the sweeps, which finish_collect turns
+    // back into d_n, e_n (composed.hpp).  Two buffers rotate; the spares are not used.
+    bool composed = false;
     // A call cut into several batches enqueues them back to back and waits once: batch `slot` of
     // `n_slots` has its own timing events and its own piece of the pinned result buffer.
     int slot = 0, n_slots = 1, ev_base = 0;
@@ -180,6 +187,19 @@ struct Batch {
             march_fixed = kind == 3;
         }
         if (march) launch_grid = splan.args.n_cols * splan.args.n_segs;  // dot partials per (step, unit)
+        // Composed sweeps: random-start runs of a whole matrix that take cheb_sweep3 with one launch per sweep, where the form
+        // exists (dictionary forms of the particle-hole modes).  Unit starts (their band of planes grows by one plane per
+        // step, not by three per level pair), slabs and the persistent kernel keep the classic body.  So does any run with
+        // BODGE_AMD_MARCH set, 0 included: that knob compares launch structures of ONE body, byte for byte in their perf
+        // records, and its one-launch-per-sweep arm is the classic sweep.  BODGE_AMD_SWEEP_COMPOSED=0|1 overrides the default.
+        composed = sweep && splan.depth == 3 && splan.composed && splan.composed_reverse && splan.composed_gen && !march &&
+                   knob::raw("BODGE_AMD_MARCH") == nullptr &&
+                   start.kind == StartKind::Random && sys->ncols == sys->nb && sys->row_offset == 0 && !sys->slab_comm &&
+                   sys->group_rows == 0;
+        {
+            const char* env = knob::raw("BODGE_AMD_SWEEP_COMPOSED");
+            composed = composed && (env ? atoi(env) != 0 : kComposedDefault);
+        }
 
         vec_count = (size_t)4 * sys->ncols * rl;  // 16-byte lane payloads
         // t_n and t_{n-1} together beyond the 256 MB Infinity Cache: the write of t_{n+1} and the
@@ -195,10 +215,13 @@ struct Batch {
         if (int rc = ss->vec_a.reserve(vec_count)) return rc;
         if (int rc = ss->vec_b.reserve(vec_count)) return rc;
         if (sweep) {
-            if (int rc = ss->vec_c.reserve(vec_count)) return rc;
-            if (int rc = ss->vec_d.reserve(vec_count)) return rc;
-            spare1 = ss->vec_c.ptr;
-            spare2 = ss->vec_d.ptr;
+            spare1 = spare2 = nullptr;
+            if (!composed) {  // (a composed batch rotates vec_a and vec_b only)
+                if (int rc = ss->vec_c.reserve(vec_count)) return rc;
+                if (int rc = ss->vec_d.reserve(vec_count)) return rc;
+                spare1 = ss->vec_c.ptr;
+                spare2 = ss->vec_d.ptr;
+            }
             splan.args.stream = 2 * vec_count * sizeof(double2) > kStreamVectorBytes ? 1 : 0;
             if (const char* env = knob::raw("BODGE_AMD_SWEEP_STREAM")) splan.args.stream = std::atoi(env);
         }
@@ -232,7 +255,7 @@ struct Batch {
         const int fill_grid = (int)std::min<size_t>(4096, (vec_count + 255) / 256);
         // Three-step sweeps make a random t_0 in registers during the first sweep (cheb_sweep3 GEN):
         // no fill kernel, and vec_a is only ever a spare buffer.  BODGE_AMD_SWEEP_GEN=0: fill and read.
-        gen_start = sweep && splan.depth == 3 && splan.kernel_gen && start.kind == StartKind::Random &&
+        gen_start = sweep && splan.depth == 3 && (composed ? splan.composed_gen : splan.kernel_gen) && start.kind == StartKind::Random &&
                     sys->row_offset == 0 && sys->ncols == sys->nb;
         if (const char* env = knob::raw("BODGE_AMD_SWEEP_GEN")) gen_start = gen_start && atoi(env) != 0;
         if (gen_start) {
@@ -579,8 +602,20 @@ struct Batch {
         a.partial1 = ss->partial.ptr + (size_t)in_chunk * per_step;
         a.partial2 = a.partial1 + per_step;
         a.partial3 = a.partial2 + per_step;
-        const SweepKernel kernel = n == 0 && gen_start ? splan.kernel_gen
-                                   : alternate && (n_launches & 1) ? splan.kernel_reverse : splan.kernel;
+        SweepKernel kernel = n == 0 && gen_start ? splan.kernel_gen
+                             : alternate && (n_launches & 1) ? splan.kernel_reverse : splan.kernel;
+        // Composed: (u_k, u_{k-1}) -> (u_{k+1} where u_{k-1} was, u_k).  Only a launch of three steps that does not discard
+        // reads u_{k-1} and stores u_{k+1}; any other is the last of its run and takes dot products only (with
+        // BODGE_AMD_KEEP_LAST a tail of one or two steps stores the last level it makes, which nothing reads).
+        // A generated u_0 is kept where t_0 would be.
+        const bool composed_stores = composed && now == 3 && !a.discard;
+        if (composed) {
+            kernel = n == 0 && gen_start ? splan.composed_gen : alternate && (n_launches & 1) ? splan.composed_reverse : splan.composed;
+            a.prev = n == 0 || !composed_stores ? nullptr : prev;
+            a.out1 = n == 0 && gen_start ? cur : nullptr;
+            a.out2 = prev;
+            a.coef1 = 1.0 / scale;
+        }
         if (n == 0 && gen_start) a.cur = nullptr;  // (never read)
         a.x_lo = 0;
         a.x_hi = a.lx;
@@ -591,14 +626,24 @@ struct Batch {
         a.n_segs = splan.segments_for(a.x_hi - a.x_lo);
         // sweep_bytes counts two buffers read and two written: t_{-1} = 0 is never read, a generated t_0 neither,
         // a lone step makes one new level, the last sweep of a run stores nothing; a band is its share of the planes
-        bytes_moved += (sweep_bytes(sys, mode, rl) -
-                        vector_bytes() * ((n == 0 ? 1 : 0) + (n == 0 && gen_start ? 1 : 0) + (a.discard ? 2 : now == 1 ? 1 : 0))) *
-                       ((double)(a.x_hi - a.x_lo) / a.lx);
+        if (composed) {
+            // three passes: u_k read, u_{k-1} read, u_{k+1} written.  The first sweep reads no u_{k-1}, and no u_0 either when it
+            // generates it - but then writes it for the second sweep; a launch that discards reads u_k only.
+            const bool generates = n == 0 && gen_start;
+            const int passes = (generates ? 0 : 1) + (composed_stores && n > 0 ? 1 : 0) + (a.discard ? 0 : 1) + (composed_stores && generates ? 1 : 0);
+            bytes_moved += sweep_bytes(sys, mode, rl) - vector_bytes() * (4 - passes);
+        } else {
+            bytes_moved += (sweep_bytes(sys, mode, rl) -
+                            vector_bytes() * ((n == 0 ? 1 : 0) + (n == 0 && gen_start ? 1 : 0) + (a.discard ? 2 : now == 1 ? 1 : 0))) *
+                           ((double)(a.x_hi - a.x_lo) / a.lx);
+        }
         kernel<<<splan.grid, splan.wg_waves * bdg::kWave, splan.lds_bytes, st>>>(a);
         ++n_launches;
         double2* old_cur = cur;
         double2* old_prev = prev;
-        if (splan.depth == 2 && now == 1) {  // cheb_sweep writes a lone step to out1
+        if (composed) {
+            if (composed_stores) std::swap(cur, prev);
+        } else if (splan.depth == 2 && now == 1) {  // cheb_sweep writes a lone step to out1
             cur = spare1;
             prev = old_cur;
             spare1 = old_prev;
@@ -687,14 +732,20 @@ struct Batch {
             HIP_TRY(hipEventElapsedTime(&ms, ss->ev_pool[2 * (ev_base + c)], ss->ev_pool[2 * (ev_base + c) + 1]));
             kernel_ms += ms;
         }
-        for (int n = 0; n < n_steps; ++n)
-            for (int r = 0; r < n_active; ++r) {
+        std::vector<double> turned;  // composed sweeps: d_n, e_n of one vector, recovered from the sweeps' own products
+        if (composed) turned.resize((size_t)2 * n_steps);
+        for (int r = 0; r < n_active; ++r) {
+            if (composed)
+                bdg_host::composed_dots_vector(n_steps, host + 2 * r, width, turned.data(), turned.data() + n_steps, 1);
+            for (int n = 0; n < n_steps; ++n) {
                 double& d = d_out[(size_t)n * ld + col0 + r];
                 double& e = e_out[(size_t)n * ld + col0 + r];
-                const double dv = host[(size_t)n * width + 2 * r], ev = host[(size_t)n * width + 2 * r + 1];
+                const double dv = composed ? turned[(size_t)n] : host[(size_t)n * width + 2 * r];
+                const double ev = composed ? turned[(size_t)n_steps + n] : host[(size_t)n * width + 2 * r + 1];
                 d = accumulate ? d + dv : dv;
                 e = accumulate ? e + ev : ev;
             }
+        }
         bdg_perf& p = sys->perf;
         if (first_batch) p = bdg_perf{};
         p.kernel_ms += kernel_ms;
@@ -703,7 +754,9 @@ struct Batch {
         p.window_ms = p.kernel_ms;  // (batches side by side on several streams: run_recurrence measures the window)
         p.streams = 1;
         p.vector_steps += (int64_t)n_steps * n_active;
-        p.bytes_per_launch = sweep  ? sweep_bytes(sys, mode, rl)
+        p.composed = composed ? 1 : 0;
+        p.bytes_per_launch = composed ? sweep_bytes(sys, mode, rl) - vector_bytes()  // (three passes instead of four)
+                             : sweep  ? sweep_bytes(sys, mode, rl)
                              : roll ? roll_bytes(sys, mode, rl)
                                     : algorithmic_bytes(sys, rv, mode, plan.dictionary);
         p.steps_per_launch = sweep ? splan.depth : 1;

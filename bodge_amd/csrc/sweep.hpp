@@ -584,7 +584,10 @@ struct Sweep3Task {
     int discard;
 };
 
-template <typename Mode, int RL, bool GEN, int OS, bool WT>
+// COMP: the composed form (see "K7b, composed" below cheb_sweep3): t.cur = u_k, t.prev = u_{k-1} (owned slots only, nullptr in
+// the first sweep of a run and in a launch that stores nothing), t.out2 = where u_{k+1} goes (the buffer of u_{k-1}: in place),
+// t.out1 = where a generated u_0 is kept (GEN), t.coef1 = 1 / scale in every sweep.
+template <typename Mode, int RL, bool GEN, int OS, bool WT, bool COMP = false>
 __device__ __forceinline__ void sweep3_unit(const SweepArgs& a, const Sweep3Task& t, const Sweep3Lds& w, const Sweep3Gen& gen, int lane,
                                             int seg, int col, bool rev, double (&dot1)[4], double (&dot2)[4], double (&dot3)[4]) {
     constexpr int SLOTS = kWave / RL;
@@ -857,7 +860,12 @@ __device__ __forceinline__ void sweep3_unit(const SweepArgs& a, const Sweep3Task
     cur_plane(k_first - 1, valid, cn_m);
     cur_plane(k_first, valid, buf_a);
     cur_plane(k_first + 1, valid, buf_b);
-    load_plane(t.prev, nt_prev, k_first, !GEN && ok1 && t.prev != nullptr, pv);  // (GEN: t_{-1} = 0)
+    if constexpr (COMP) {  // (`pv` is u_{k-1} of the plane step 3 works on next: nothing before the march's fifth plane)
+#pragma unroll
+        for (int al = 0; al < 4; ++al) pv[al] = zero;
+    } else {
+        load_plane(t.prev, nt_prev, k_first, !GEN && ok1 && t.prev != nullptr, pv);  // (GEN: t_{-1} = 0)
+    }
     uint2 ids_0 = load_ids(k_first), ids_1 = make_uint2(0xFFFFFFFFu, 0xFFu), ids_2 = ids_1;
 #pragma unroll
     for (int al = 0; al < 4; ++al) c1_m[al] = c2_m[al] = zero;
@@ -889,17 +897,28 @@ __device__ __forceinline__ void sweep3_unit(const SweepArgs& a, const Sweep3Task
             apply(ids_0, cn_m, row_0, mid, after, acc, k);
 #pragma unroll
             for (int al = 0; al < 4; ++al) {
-                new1[al].x = fma(t.coef1, acc[al].x, -pv[al].x);
-                new1[al].y = fma(t.coef1, acc[al].y, -pv[al].y);
+                if constexpr (COMP) {  // w_1 = H u / scale: nothing is subtracted (what the classic form makes of t_{-1} = 0)
+                    new1[al].x = t.coef1 * acc[al].x;
+                    new1[al].y = t.coef1 * acc[al].y;
+                } else {
+                    new1[al].x = fma(t.coef1, acc[al].x, -pv[al].x);
+                    new1[al].y = fma(t.coef1, acc[al].y, -pv[al].y);
+                }
             }
             if (owned && k >= x0 && k < x1) {
 #pragma unroll
                 for (int al = 0; al < 4; ++al) Mode::dots(dot1, mid[al], new1[al]);
+                // (COMP: a tail launch of one or two steps discards - unless the run keeps its last vectors, BODGE_AMD_KEEP_LAST:
+                // then it stores the last level it makes, as any launch does)
                 if (steps == 1) store_plane(t.out2, k, new1);
-                if (steps == 2) store_plane(t.out1, k, new1);
+                if constexpr (!COMP) {
+                    if (steps == 2) store_plane(t.out1, k, new1);
+                } else if constexpr (GEN) {
+                    if (steps == 3) store_plane(t.out1, k, mid);  // the generated u_0: the second sweep reads it at the owned slots
+                }
             }
         }
-        load_plane(t.prev, nt_prev, k + 1, !GEN && ok1 && more && t.prev != nullptr, pv);
+        if constexpr (!COMP) load_plane(t.prev, nt_prev, k + 1, !GEN && ok1 && more && t.prev != nullptr, pv);
 
         // ---- step 2 on plane k-1: level 2 = c2 H level1 - t_n        (row_1 = level 1, plane k-1)
         if (steps >= 2 && ok2 && in_lattice(k - 1) && k - 1 >= x0 - (steps - 2) && k - 1 < x1 + (steps - 2)) {
@@ -917,7 +936,8 @@ __device__ __forceinline__ void sweep3_unit(const SweepArgs& a, const Sweep3Task
 #pragma unroll
                 for (int al = 0; al < 4; ++al) Mode::dots(dot2, mid[al], new2[al]);
                 if (steps == 2) store_plane(t.out2, k - 1, new2);
-                if (steps == 3) store_plane(t.out1, k - 1, new2);
+                if constexpr (!COMP)
+                    if (steps == 3) store_plane(t.out1, k - 1, new2);
             }
         }
 
@@ -943,8 +963,22 @@ __device__ __forceinline__ void sweep3_unit(const SweepArgs& a, const Sweep3Task
                 new3[al].y = fma(a.coef2, acc[al].y, -c1_m[al].y);
                 Mode::dots(dot3, mid[al], new3[al]);
             }
+            if constexpr (COMP) {
+                // u_{k+1} = 2 w_3 - u_{k-1}, to where u_{k-1} was read from; the first sweep of a run has no u_{k-1}: u_1 = w_3
+                if (t.prev != nullptr) {  // (uniform)
+#pragma unroll
+                    for (int al = 0; al < 4; ++al) {
+                        new3[al].x = fma(2.0, new3[al].x, -pv[al].x);
+                        new3[al].y = fma(2.0, new3[al].y, -pv[al].y);
+                    }
+                }
+            }
             store_plane(t.out2, k - 2, new3);
         }
+        // (COMP) u_{k-1} of plane k-1, where step 3 works in the next iteration: asked for a whole iteration ahead, by the
+        // owned lanes only (every other lane an offset out of range), and only by a launch that stores
+        if constexpr (COMP)
+            load_plane(t.prev, nt_prev, k - 1, owned && more && steps == 3 && t.prev != nullptr && k - 1 >= x0 && k - 1 < x1, pv);
 
         // ---- roll: every level moves one plane on
         wave_sync();
@@ -1001,8 +1035,8 @@ __device__ inline Sweep3Lds sweep3_stage_lds(double2* lds, const SweepArgs& a, i
 // WAVES: waves per workgroup.  4 with two workgroups per CU is the default; the streamed forms whose ring of records
 // leaves room for fewer than eight waves on a CU run ONE workgroup of 5..7 waves per CU instead (160 KB of LDS: seven
 // waves of 12 KB rows + a ring of up to 10.5 KB), which keeps 2 lanes per site (32-slot windows) within reach.
-template <typename Mode, int RL, bool REV, bool GEN = false, int OS = 0, int WAVES = kWavesPerBlock>
-__global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 1 : 2) void cheb_sweep3(SweepArgs a) {
+template <typename Mode, int RL, bool REV, bool GEN, int OS, int WAVES, bool COMP>
+__device__ __forceinline__ void sweep3_launch(const SweepArgs& a) {
     extern __shared__ double2 lds[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -1022,7 +1056,7 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 1 : 2) void cheb_sweep3(
     for (int u = u_lo + (int)(blockIdx.x >> 3) * WAVES + wave; u < u_hi; u += waves_per_xcd) {
         const int seg = u / a.n_cols, col = u - seg * a.n_cols;
         const bool rev = REV != (bool)(a.zigzag & seg & 1);  // wave-uniform
-        sweep3_unit<Mode, RL, GEN, OS, false>(a, task, w, gen, lane, seg, col, rev, dot1, dot2, dot3);
+        sweep3_unit<Mode, RL, GEN, OS, false, COMP>(a, task, w, gen, lane, seg, col, rev, dot1, dot2, dot3);
     }
 
     const int steps = a.steps;
@@ -1036,6 +1070,28 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 1 : 2) void cheb_sweep3(
         __syncthreads();
         sweep_reduce_dots<Mode, RL, WAVES>(dot3, reinterpret_cast<double*>(lds), a.partial3, lane, wave);
     }
+}
+
+template <typename Mode, int RL, bool REV, bool GEN = false, int OS = 0, int WAVES = kWavesPerBlock>
+__global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 1 : 2) void cheb_sweep3(SweepArgs a) {
+    sweep3_launch<Mode, RL, REV, GEN, OS, WAVES, false>(a);
+}
+
+// K7b, composed: step by T_3(H~).  The Chebyshev polynomials compose, T_{3(k+1)} = 2 T_3 T_{3k} - T_{3(k-1)}, so with u_k = t_{3k}
+//     u_{k+1} = 2 T_3(H~) u_k - u_{k-1},    T_3(H~) u = w_3:   w_1 = H~ u,  w_2 = 2 H~ w_1 - u,  w_3 = 2 H~ w_2 - w_1.
+// A sweep reads u_k with halos exactly as t_n is read above, makes the same three block-stencil products, reads u_{k-1} at
+// the owned slots only and writes only u_{k+1}, over u_{k-1}: THREE array passes per three steps instead of four (a lane
+// reads an address before it writes it, and no other wave touches u_{k-1}).  What changes in the unit body (COMP): level 1
+// subtracts nothing and its coefficient is 1 / scale in every sweep, no level is stored but the last, and that one as
+// 2 w_3 - u_{k-1} (w_3 itself in the first sweep of a run: u_1 = T_3 u_0).  The halo lanes load no t_{n-1} any more.  A launch that
+// makes fewer than three steps (the tail of a run) or discards stores nothing at all: it only takes dot products.
+// The levels inside a sweep are w_j = (t_{3k+j} + t_{3k-j}) / 2, not t_{3k+j}: the six dot products of a sweep are
+// <u|u>, <w_1|u>, <w_1|w_1>, <w_2|w_1>, <w_2|w_2>, <w_3|w_2>, from which the host recovers d_n and e_n exactly (composed.hpp).
+// GEN: the first sweep keeps the u_0 it generates (owned slots, t.out1) for the second sweep - one pass per run.
+// Dictionary forms (no streamed records), four waves per workgroup.
+template <typename Mode, int RL, bool REV, bool GEN = false>
+__global__ __launch_bounds__(kWavesPerBlock * kWave, 2) void cheb_sweep3_composed(SweepArgs a) {
+    sweep3_launch<Mode, RL, REV, GEN, 0, kWavesPerBlock, true>(a);
 }
 
 // =====================================================================================

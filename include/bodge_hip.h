@@ -104,6 +104,11 @@ typedef struct bdg_perf {
                               (cheb_family / cheb_family_dict with GreenBondTail); 0 = the call was another one */
     int32_t roll_chunk;    /* cheb_roll3: plane-steps per unit (RollArgs.chunk) of the last rolling launch of the batch the
                               record describes; 0 = whole-column segments, and 0 when the call did not roll */
+    int32_t composed;      /* 1 = the three-step sweeps of the call were composed ones (cheb_sweep3_composed: every launch steps
+                              by T_3(H/scale), three array passes per three steps, updating t_{3(k-1)} to t_{3(k+1)} in place;
+                              steps_per_launch stays 3 and bytes_per_launch is the three-pass launch); 0 = classic sweeps, or
+                              the call was another one.  (response_map moved into what was padding before gemm_ms: the
+                              record keeps its size and no other field moved.) */
     int32_t response_map;  /* bdg_response_map: 1 = the call was this one, 0 = another one */
     double gemm_ms;        /* bdg_response_map: HIP-event time of its product launches (resp_gemm) */
     double gemm_flops;     /* bdg_response_map: 8 x n_moments^2 x K summed over the chunks of sites and the kernels, K = 4 x
@@ -501,6 +506,18 @@ int bdg_host_scan_blocks(const double* data, const int32_t* indptr, int64_t nb, 
                          double* ph_defect, double* row_sum_max, int32_t* all_real);
 int bdg_host_compact_blocks(const double* data, const int32_t* indices, const int32_t* indptr, int64_t nb,
                             const uint8_t* keep, double* data_out, int32_t* indices_out, int32_t* indptr_out);
+
+/*
+ * Host arithmetic of the composed three-step sweep (bdg_perf.composed; CPU only, no device call, usable without a
+ * GPU).  Such a run steps by T_3(H/scale): sweep k starts from u = t_{3k} and makes w_j = T_j(H/scale) u =
+ * (t_{3k+j} + t_{3k-j}) / 2, and row n = 3k + j of its dot table holds <w_j|w_j>, Re <w_{j+1}|w_j> instead of d_n, e_n.
+ * This function turns such a table back:  raw[n * raw_stride + 2 * r + {0, 1}] are the two products of row n < n_steps
+ * and vector r < n_vectors (raw_stride >= 2 * n_vectors doubles per row); d_out / e_out [n * ld + r] receive
+ * <t_n|t_n> and Re <t_{n+1}|t_n> (ld >= n_vectors).  Every new moment is a measured product minus older moments, so
+ * rounding errors add and are not amplified; d_{3k} is handed through bit for bit.  Any n_steps >= 1.
+ */
+int bdg_host_composed_dots(int32_t n_steps, int32_t n_vectors, const double* raw, int64_t raw_stride, double* d_out,
+                           double* e_out, int64_t ld);
 
 /*
  * Optional: start reading the rocSOLVER / rocBLAS shared objects into the page cache on a

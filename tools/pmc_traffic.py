@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Turn rocprofv3 PMC passes into per-launch HBM traffic of the recurrence kernel.
 
-    # on the GPU box, one pass per counter (FETCH_SIZE and WRITE_SIZE do not fit one pass):
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d OUT/pmc_FETCH_SIZE -- python3 bench.py --full --steps 8 --warmup 2 --cpu-seconds 0
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d OUT/pmc_WRITE_SIZE -- python3 bench.py --full --steps 8 --warmup 2 --cpu-seconds 0
+    # on the GPU box, one pass per counter (FETCH_SIZE and WRITE_SIZE do not fit one pass), no tracing beside the counters
+    # (add --full --cpu-seconds 0 for the kernels of the comparison passes):
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc_FETCH_SIZE -- python3 bench.py --steps 32 --warmup 2
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/pmc_WRITE_SIZE -- python3 bench.py --steps 32 --warmup 2
     # then, anywhere:
     python3 tools/pmc_traffic.py OUT/pmc_FETCH_SIZE OUT/pmc_WRITE_SIZE --workload "1000x1000x1 R=8" --out profiles/traffic.json
 
@@ -32,6 +33,11 @@ def kernel_key(name: str) -> str:
         if m.group(3) == "true":
             return ""
         return f"cheb_sweep3<{m.group(1)},{m.group(2)}{ {'0': '', '1': ',onsite-streamed', '2': ',all-blocks-streamed'}[m.group(4)] }>"
+    # cheb_sweep3_composed<Mode, lanes, REV, GEN>: the composed form of the dictionary sweep.  It takes the place of
+    # cheb_sweep3<Mode, lanes> in random-start runs, and bench.py names the headline kernel by that instance: same key
+    m = re.search(r"cheb_sweep3_composed<bdg::(\w+), (\d), (?:true|false), (true|false)>", name)
+    if m:
+        return "" if m.group(3) == "true" else f"cheb_sweep3<{m.group(1)},{m.group(2)}>"
     m = re.search(r"cheb_sweep<bdg::(\w+), (\d), (?:true|false)>", name)
     if m:
         return f"cheb_sweep<{m.group(1)},{m.group(2)}>"
