@@ -24,6 +24,7 @@ _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u8p = C.POINTER(C.c_uint8)
+_i8p = C.POINTER(C.c_int8)
 _handle = C.c_void_p
 
 
@@ -64,6 +65,7 @@ class Perf(C.Structure):
         ("response_map", C.c_int32),
         ("gemm_ms", C.c_double),
         ("gemm_flops", C.c_double),
+        ("green_probe", C.c_int32),
         ("correlation", C.c_int32),
         ("gram_ms", C.c_double),
         ("gram_flops", C.c_double),
@@ -117,6 +119,9 @@ SIGNATURES = {
     "bdg_green_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, C.c_int32, _i32p, _f64p]),
     "bdg_green_local_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i32p, C.c_int32, _f64p]),
     "bdg_green_bond_blocks": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, _i32p, _i32p, C.c_int32, _f64p]),
+    "bdg_green_probe_blocks": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _i32p, C.c_int32, _i8p,
+                                        _i32p, _i32p, C.c_int32, _f64p, _f64p]),
+    "bdg_host_probe_check": (C.c_int, [C.c_int64, C.c_int32, _i32p, C.c_int32, _i8p, _i32p, _i32p, C.c_int32]),
     "bdg_green_state_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _f64p, C.c_int32, _f64p]),
     "bdg_cheb_diag_moments": (C.c_int, [_handle, C.c_double, C.c_int32, C.c_int32, _i64p, _f64p]),
     "bdg_lanczos_begin": (C.c_int, [_handle, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
@@ -213,6 +218,10 @@ def as_i32p(array: np.ndarray):
 
 def as_i64p(array: np.ndarray):
     return array.ctypes.data_as(_i64p)
+
+
+def as_i8p(array: np.ndarray):
+    return array.ctypes.data_as(_i8p)
 
 
 def as_u8p(array: np.ndarray):

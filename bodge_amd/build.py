@@ -19,7 +19,7 @@ INCLUDE = os.path.join(os.path.dirname(ROOT), "include")
 LIBRARY = os.path.join(CSRC, "libbodge_hip.so")
 SOURCES = [os.path.join(CSRC, "bodge_hip.hip")]
 HEADERS = [os.path.join(CSRC, name) for name in (
-    "kernels.hpp", "sweep.hpp", "twostage.hpp", "host_assembly.hpp", "core.hpp", "plans.hpp", "libraries.hpp", "recurrence.hpp", "family.hpp", "fermi.hpp", "apply.hpp", "correlation.hpp", "response_map.hpp", "green_driver.hpp", "green.hpp", "green_map.hpp", "green_bonds.hpp", "green_states.hpp",
+    "kernels.hpp", "sweep.hpp", "twostage.hpp", "host_assembly.hpp", "core.hpp", "plans.hpp", "libraries.hpp", "recurrence.hpp", "family.hpp", "fermi.hpp", "apply.hpp", "correlation.hpp", "response_map.hpp", "green_driver.hpp", "green.hpp", "green_map.hpp", "green_bonds.hpp", "green_probe.hpp", "green_states.hpp",
     "lanczos.hpp", "subspace.hpp", "dense.hpp", "tridiag.hpp", "knobs.hpp", "composed.hpp")] + [os.path.join(INCLUDE, "bodge_hip.h")]
 ARCH = "gfx950"
 

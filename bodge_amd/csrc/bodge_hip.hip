@@ -13,7 +13,7 @@
 //   libraries.hpp   rocSOLVER / rocBLAS / RCCL via dlopen, background prefetch of the shared objects
 //   recurrence.hpp  Batch (begin / step / finish), run_recurrence, run_group
 //   family.hpp      the two tile loops, dispatch, launch plan, width rules and set-up shared by fermi / apply /
-//                   correlation / response_map / green / green_map / green_bonds / green_states.hpp; the rounds of
+//                   correlation / response_map / green / green_map / green_bonds / green_probe / green_states.hpp; the rounds of
 //                   batches side by side of fermi / apply
 //   green_driver.hpp  the batches x ranges x moments loop shared by green / green_map / green_bonds / green_states.hpp
 //   lanczos.hpp     Lanczos on H^2 (device-resident scalars)
@@ -73,6 +73,7 @@
 #include "green.hpp"
 #include "green_map.hpp"
 #include "green_bonds.hpp"
+#include "green_probe.hpp"
 #include "green_states.hpp"
 #include "lanczos.hpp"
 #include "subspace.hpp"
@@ -708,6 +709,24 @@ int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, in
 int bdg_green_bond_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
                           const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* out) {
     return run_green_bond_blocks(sys, scale, n_moments, n_weights, weights, pat_indptr, pat_indices, n_components, out);
+}
+
+int bdg_green_probe_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
+                           int32_t n_colours, const int32_t* site_colour, int32_t n_samples, const int8_t* signs,
+                           const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* mean_out,
+                           double* stderr_out) {
+    return run_green_probe_blocks(sys, scale, n_moments, n_weights, weights, n_colours, site_colour, n_samples, signs,
+                                  pat_indptr, pat_indices, n_components, mean_out, stderr_out);
+}
+
+int bdg_host_probe_check(int64_t nb, int32_t n_colours, const int32_t* site_colour, int32_t n_samples, const int8_t* signs,
+                         const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components) {
+    if (nb < 1) return fail(BDG_EINVAL, "nb must be >= 1");
+    if (n_colours < 1) return fail(BDG_EINVAL, "n_colours must be >= 1");
+    if (n_samples < 1) return fail(BDG_EINVAL, "n_samples must be >= 1");
+    if (!site_colour || !pat_indptr || !pat_indices) return fail(BDG_EINVAL, "null argument");
+    if (!signs && n_samples > 1) return fail(BDG_EINVAL, "signs must be given for more than one sample");
+    return green_probe_check(nb, n_colours, site_colour, n_samples, signs, pat_indptr, pat_indices, n_components);
 }
 
 int bdg_green_state_moments(bdg_system* sys, double scale, int32_t n_moments, int32_t n_states,

@@ -13,8 +13,15 @@ the GPU, and every step stores the rows of the target sites (`bdg_green_moments`
     G(z)[ja, ib] = -i / (a·sqrt(1 - z̃²)) · Σ_n (2 - δ_n0) · exp(-i·n·arccos z̃) · μ_n[ja, ib],   z̃ = z/a.
 
 With particle-hole symmetry (H = -τx H* τx) only the electron columns b = 0, 1 are run; the hole columns are
-μ_n[a, b] = (-1)ⁿ·conj μ_n[a⊕2, b⊕2].  Probing several sources with one vector does not work here: G(ε + iΓ)
-decays far too slowly with distance, so every source site gets its own start vectors.
+μ_n[a, b] = (-1)ⁿ·conj μ_n[a⊕2, b⊕2].  G(ε + iΓ) decays slowly with distance in a band at small Γ, so by default
+every source site gets its own start vectors; `green_map` and `green_bonds` probe several sources with one vector on
+request (`distance=`, below).
+
+Probing: `green_map(distance=d)` and `green_bonds(distance=d)` colour the sites as `fermi_matrix` does
+and start one vector per colour and Nambu column, the sum of the colour's unit vectors with signs ξ = ±1
+(`bdg_green_probe_blocks`).  The number of vectors no longer grows with the lattice; a block carries the other sites of
+its colour, Σ ξ_i ξ_i' G_ji', a bias with ξ = +1 and zero-mean noise with random signs, whose mean and standard error
+over `samples` are taken on the device.
 
 Maps: `green_map` wants the local block G_jj at many sites j.  The start vectors of up to 32
 sites share one batch of the recurrence, and a step stores for every vector the rows of its own site only
@@ -181,20 +188,97 @@ def green(system, source: Coord, energies, targets=None, *, broadening=None, mom
     return GreenFunction(np.ascontiguousarray(blocks[where.reshape(-1)]), energies, gamma, source, targets, info)
 
 
+# ---------------------------------------------------------------- probing
+def z2_signs(seed: int, samples: int, n_sites: int) -> np.ndarray:
+    """(samples, n_sites) int8 of ±1: sample s is np.random.default_rng(seed + s).choice([-1, 1], n_sites)."""
+    return np.stack([np.random.default_rng(int(seed) + s).choice([-1, 1], n_sites) for s in range(samples)]).astype(np.int8)
+
+
+def _probe_arguments(system, distance, samples, seed, signs, wanted: np.ndarray):
+    """Colours and signs of a probed call, checked.  `wanted` (N,) bool marks the source sites; returns (colour (N,)
+    int32 with -1 off the source sites and the colours in use numbered from 0, their number, the colour periods of a
+    cubic lattice or None, signs (samples, N) int8 or None for one sample of all +1, samples)."""
+    from . import fermi
+    from .lattice import CubicLattice
+
+    n = system.lattice.size
+    distance, samples = int(distance), int(samples)
+    if distance < 3:
+        raise ValueError("green: distance must be >= 3 (or None for one start vector per site)")
+    if samples < 1:
+        raise ValueError("green: samples must be >= 1")
+    if signs is None:
+        signs = "z2" if samples > 1 else None
+    if isinstance(signs, str):
+        if signs != "z2":
+            raise ValueError(f"green: signs must be None, 'z2' or a (samples, N) array of ±1, not {signs!r}")
+        signs = z2_signs(seed, samples, n)
+    elif signs is not None:
+        signs = np.asarray(signs)
+        if signs.shape != (samples, n):
+            raise ValueError(f"green: signs of shape {signs.shape} for {samples} samples of {n} sites")
+        if not np.all(np.abs(signs) == 1) or np.iscomplexobj(signs):
+            raise ValueError("green: only signs of +1 and -1 are supported")
+        signs = signs.astype(np.int8)
+    if samples > 1 and (signs is None or np.all(signs == 1)):
+        raise ValueError("green: samples > 1 needs random signs (all +1 gives the same sample every time)")
+    colour, _ = fermi.site_colours(system, distance)
+    colour = np.array(colour, dtype=np.int32)
+    colour[~wanted] = -1
+    used, compact = np.unique(colour[wanted], return_inverse=True)
+    colour[wanted] = compact.astype(np.int32)
+    periods = None
+    if isinstance(system.lattice, CubicLattice):
+        periods = fermi.colour_periods(system.lattice.shape, distance)
+    return colour, int(used.size), periods, signs, samples
+
+
+def _probed_blocks(solver, scale, weights, n_sites, rows, cols, columns, colour, n_colours, signs):
+    """The probed blocks on the pattern (rows, cols) (canonical order) and their standard error or None, (nnz, K, 4, 4),
+    with the perf records: groups of whole colours whose result (energies x blocks x 256 B) stays within the host
+    limit; the sites of the other groups take no part in a group's call (colour -1)."""
+    per_colour = np.bincount(colour[cols], minlength=n_colours) * weights.shape[0] * 256
+    blocks = np.empty((cols.size, weights.shape[0], 4, 4), dtype=np.complex128)
+    stderr = np.empty_like(blocks) if signs is not None and signs.shape[0] > 1 else None
+    perf, lo = [], 0
+    while lo < n_colours:
+        hi = lo + max(1, int(np.searchsorted(np.cumsum(per_colour[lo:]), HOST_TABLE_LIMIT, side="right")))
+        full = 64 // columns  # colours of the widest device batch; narrower ones (a power of two less) divide it
+        if hi < n_colours and hi - lo > full:
+            hi -= (hi - lo) % full  # (whole device batches, whatever the width: no group ends on a part-filled one)
+        hi = min(hi, n_colours)
+        part = np.flatnonzero((colour[cols] >= lo) & (colour[cols] < hi))
+        part_indptr = np.zeros(n_sites + 1, dtype=np.int32)
+        np.cumsum(np.bincount(rows[part], minlength=n_sites), out=part_indptr[1:])
+        group = np.where((colour >= lo) & (colour < hi), colour - lo, -1).astype(np.int32)
+        mean, error = solver.green_probe_blocks(scale, weights, group, hi - lo, part_indptr, cols[part].astype(np.int32),
+                                                columns, signs)
+        perf.append(solver.perf())
+        blocks[part] = mean.transpose(1, 0, 2, 3)
+        if stderr is not None:
+            stderr[part] = error.transpose(1, 0, 2, 3)
+        lo = hi
+    return blocks, stderr, perf
+
+
 class GreenMap:
     """Local blocks of G(ε + iΓ) at many sites.
 
     `blocks` (S, K, 4, 4) complex128: blocks[s, k] = G(E_k + iΓ_k)[4j_s:4j_s+4, 4j_s:4j_s+4]; `energies` and
     `broadening` (K,), `sites` the lattice coordinates, `info` the route details as in `GreenFunction`.  The
-    helpers are those of `GreenFunction` with one leading site axis more.
+    helpers are those of `GreenFunction` with one leading site axis more.  `stderr` is None, or for a probed call with
+    two samples or more an array of the shape of `blocks`: the standard error of the mean over the samples,
+    sqrt(Σ(x - mean)² / (S(S - 1))), of Re in its real part and of Im in its imaginary part.
     """
 
-    def __init__(self, blocks: np.ndarray, energies: np.ndarray, broadening: np.ndarray, sites, info: dict | None = None):
+    def __init__(self, blocks: np.ndarray, energies: np.ndarray, broadening: np.ndarray, sites, info: dict | None = None,
+                 stderr: np.ndarray | None = None):
         self.blocks = blocks
         self.energies = energies
         self.broadening = broadening
         self.sites = [tuple(site) for site in sites]
         self.info = dict(info or {})
+        self.stderr = stderr  # probed with samples >= 2: the standard error of Re (real part) and Im (imaginary part)
 
     def site(self, coord: Coord) -> np.ndarray:
         """(K, 4, 4) blocks of the site `coord` (its first position in `sites`)."""
@@ -226,8 +310,17 @@ class GreenMap:
 
 
 def green_map(system, energies, sites=None, *, broadening=None, moments: int | None = None, digits: float = 12.0,
-              scale: float | None = None, _all_columns: bool = False) -> GreenMap:
-    """Local blocks G_jj(E + iΓ) at the sites `sites` (see `Hamiltonian.green_map`)."""
+              scale: float | None = None, distance: int | None = None, samples: int = 1, seed: int = 0, signs=None,
+              _all_columns: bool = False) -> GreenMap:
+    """Local blocks G_jj(E + iΓ) at the sites `sites` (see `Hamiltonian.green_map`).
+
+    distance=None: one start vector per site and Nambu column, exact up to the truncation of the series.  distance=d
+    (>= 3) probes: the sites are coloured as for `fermi_matrix(distance=d)`, one start vector per colour and Nambu
+    column carries all sites of the colour, and a block picks up Σ ξ_j ξ_j' G_jj' over the other sites j' of its colour
+    (|G_jj'(ε + iΓ)| at range >= d: small inside a gap or at large Γ, not in a band at small Γ).
+    `signs` None: ξ = +1 (the default for samples=1, a bias); "z2": ξ = ±1 per site from `seed` (the default for
+    samples > 1: zero-mean noise, `blocks` the mean over the samples and `stderr` its standard error); or a
+    (samples, N) array of ±1.  Sites not in `sites` are no sources."""
     if sites is None:
         sites = list(system.lattice.sites())
         indices = np.arange(system.lattice.size, dtype=np.int64)
@@ -241,6 +334,21 @@ def green_map(system, energies, sites=None, *, broadening=None, moments: int | N
     distinct, where = np.unique(indices, return_inverse=True)  # (a block row is listed once in a device call)
     derive = not _all_columns and system.has_symmetric_spectrum(1e-12)
     columns = 2 if derive else 4
+
+    if distance is not None:  # probing: the diagonal blocks of the sites are the pattern
+        n = system.lattice.size
+        wanted = np.zeros(n, dtype=bool)
+        wanted[distinct] = True
+        colour, n_colours, periods, signs, samples = _probe_arguments(system, distance, samples, seed, signs, wanted)
+        weights = moment_weights(moments, scale, energies + 1j * gamma)
+        blocks, stderr, perf = _probed_blocks(system._solver(), scale, weights, n, distinct, distinct, columns, colour,
+                                              n_colours, signs)
+        info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+                "perf": perf[0] if len(perf) == 1 else perf, "distance": int(distance), "periods": periods,
+                "colours": n_colours, "samples": samples, "seed": int(seed)}
+        where = where.reshape(-1)
+        return GreenMap(np.ascontiguousarray(blocks[where]), energies, gamma, sites, info,
+                        None if stderr is None else np.ascontiguousarray(stderr[where]))
 
     solver = system._solver()
     z = energies + 1j * gamma
@@ -269,8 +377,9 @@ class GreenBonds:
     """
 
     def __init__(self, lattice, indptr: np.ndarray, indices: np.ndarray, blocks: np.ndarray, energies: np.ndarray,
-                 broadening: np.ndarray, info: dict | None = None, skeleton=None):
+                 broadening: np.ndarray, info: dict | None = None, skeleton=None, stderr: np.ndarray | None = None):
         self.lattice = lattice
+        self.stderr = stderr  # as in `GreenMap`
         self.indptr = indptr
         self.indices = indices
         self.blocks = blocks
@@ -300,7 +409,8 @@ class GreenBonds:
         diagonal = np.flatnonzero(self._rows == self.indices)
         coords = list(self.lattice.sites())
         sites = [coords[int(i)] for i in self.indices[diagonal]]
-        return GreenMap(np.ascontiguousarray(self.blocks[diagonal]), self.energies, self.broadening, sites, self.info)
+        stderr = None if self.stderr is None else np.ascontiguousarray(self.stderr[diagonal])
+        return GreenMap(np.ascontiguousarray(self.blocks[diagonal]), self.energies, self.broadening, sites, self.info, stderr)
 
     def anomalous(self, j: Coord, i: Coord) -> np.ndarray:
         """(K, 2, 2) the electron-hole block G_ji[0:2, 2:4]: the pair function on the bond (j, i)."""
@@ -354,8 +464,11 @@ class GreenBonds:
 
 
 def green_bonds(system, energies, sites=None, *, broadening=None, moments: int | None = None, digits: float = 12.0,
-                scale: float | None = None, _all_columns: bool = False) -> GreenBonds:
-    """G_ji(E + iΓ) on every skeleton block (j, i) of H with i among `sites` (see `Hamiltonian.green_bonds`)."""
+                scale: float | None = None, distance: int | None = None, samples: int = 1, seed: int = 0, signs=None,
+                _all_columns: bool = False) -> GreenBonds:
+    """G_ji(E + iΓ) on every skeleton block (j, i) of H with i among `sites` (see `Hamiltonian.green_bonds`);
+    `distance`, `samples`, `seed` and `signs` probe as in `green_map`: block (j, i) picks up Σ ξ_i ξ_i' G_ji' over the
+    other sites i' of the colour of i."""
     n = system.lattice.size
     if sites is None:
         columns_wanted = np.arange(n, dtype=np.int64)
@@ -379,6 +492,15 @@ def green_bonds(system, energies, sites=None, *, broadening=None, moments: int |
 
     derive = not _all_columns and system.has_symmetric_spectrum(1e-12)
     columns = 2 if derive else 4
+    if distance is not None:
+        colour, n_colours, periods, signs, samples = _probe_arguments(system, distance, samples, seed, signs, wanted)
+        weights = moment_weights(moments, scale, energies + 1j * gamma)
+        blocks, stderr, perf = _probed_blocks(system._solver(), scale, weights, n, rows, cols, columns, colour, n_colours,
+                                              signs)
+        info = {"moments": moments, "scale": scale, "columns": columns, "hole_columns_derived": derive,
+                "perf": perf[0] if len(perf) == 1 else perf, "distance": int(distance), "periods": periods,
+                "colours": n_colours, "samples": samples, "seed": int(seed)}
+        return GreenBonds(system.lattice, indptr, indices, blocks, energies, gamma, info, (full_indices.size, kept), stderr)
     solver = system._solver()
     weights = moment_weights(moments, scale, energies + 1j * gamma)
     # groups of source sites whose result (energies x blocks x 256 B) stays within the host limit

@@ -523,8 +523,11 @@ class Hamiltonian:
     def green_map(self, energies, sites=None, **options):
         """Local blocks G_jj(ε + iΓ) of the retarded Green's function at the sites `sites` (default: every
         site in index order), as a `GreenMap` whose slices ldos(), spin_ldos(), spin_density(), anomalous()
-        carry a leading site axis: LDOS line cuts and maps from full-width batches of the recurrence.  Not
-        part of the reference API; options (broadening, moments, digits, scale) are those of `green`."""
+        carry a leading site axis: LDOS line cuts and maps from full-width batches of the recurrence.  With
+        distance=d the sites are probed by colours as in `fermi_matrix` (samples=, seed=, signs=; the result
+        carries `stderr` for samples >= 2): maps of lattices far too large for one start vector per site, at the
+        price of the contributions of same-colour sites.  Not part of the reference API; the other options
+        (broadening, moments, digits, scale) are those of `green`."""
         from .green import green_map
 
         return green_map(self, energies, sites, **options)
@@ -534,8 +537,8 @@ class Hamiltonian:
         (the site itself, every bond and periodic-edge pair) whose column i is one of the source sites `sites`
         (default: every site), as a `GreenBonds` with block(j, i), local() (a `GreenMap`), anomalous(j, i), spectral()
         and expectation(dH): the bond pair function of d- and p-wave superconductors, the spectral current.  The
-        moments are contracted to energies on the GPU.  Not part of the reference API; options (broadening, moments,
-        digits, scale) are those of `green`."""
+        moments are contracted to energies on the GPU.  distance=, samples=, seed= and signs= probe as in `green_map`.
+        Not part of the reference API; the other options (broadening, moments, digits, scale) are those of `green`."""
         from .green import green_bonds
 
         return green_bonds(self, energies, sites, **options)

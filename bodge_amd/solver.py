@@ -348,6 +348,45 @@ class DeviceSolver:
             backend.as_i32p(indptr), backend.as_i32p(indices), int(n_components), backend.as_f64p(out.view(np.float64))))
         return out
 
+    def green_probe_blocks(self, scale, weights, colours, n_colours: int, indptr, indices, n_components: int = 4,
+                           signs=None, want_stderr: bool | None = None):
+        """(mean, stderr) of the probed blocks on the BSR pattern (`indptr`, `indices`), each (n_weights, nnz, 4, 4)
+        complex: one start vector per colour and Nambu column, `colours` (n_sites,) int32 below `n_colours` (negative:
+        no source), `signs` (samples, n_sites) of ±1 or None for one sample of all +1 (bdg_green_probe_blocks).  stderr
+        is None unless asked for (default: with two samples or more)."""
+        self._lanczos_vectors = 0  # any other use of the handle ends a Lanczos run (library: lanczos_free)
+        weights = np.ascontiguousarray(weights, dtype=np.complex128)
+        colours = np.ascontiguousarray(colours, dtype=np.int32).reshape(-1)
+        indptr = np.ascontiguousarray(indptr, dtype=np.int32).reshape(-1)
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        if weights.ndim != 2 or weights.shape[0] < 1 or weights.shape[1] < 1:
+            raise ValueError("green_probe_blocks: expected weights of shape (energies, moments)")
+        if indptr.shape != (self.n_sites + 1,) or indices.size < 1 or int(indptr[-1]) != indices.size:
+            raise ValueError(f"green_probe_blocks: the pattern does not describe the handle's {self.n_sites} block rows")
+        if colours.shape != (self.n_sites,):
+            raise ValueError(f"green_probe_blocks: expected one colour for each of the {self.n_sites} sites")
+        if int(n_components) not in (2, 4):
+            raise ValueError("green_probe_blocks: expected 2 or 4 components")
+        samples = 1
+        if signs is not None:
+            signs = np.ascontiguousarray(signs)
+            if signs.ndim != 2 or signs.shape[0] < 1 or signs.shape[1] != self.n_sites:
+                raise ValueError(f"green_probe_blocks: expected signs of shape (samples, {self.n_sites})")
+            if not np.all(np.abs(signs) == 1):
+                raise ValueError("green_probe_blocks: the signs must be +1 or -1")
+            signs = np.ascontiguousarray(signs, dtype=np.int8)
+            samples = signs.shape[0]
+        if want_stderr is None:
+            want_stderr = samples > 1
+        mean = np.empty((weights.shape[0], indices.size, 4, 4), dtype=np.complex128)
+        stderr = np.empty_like(mean) if want_stderr else None
+        backend.check(self._lib.bdg_green_probe_blocks(
+            self._handle, float(scale), weights.shape[1], weights.shape[0], backend.as_f64p(weights.view(np.float64)),
+            int(n_colours), backend.as_i32p(colours), samples, None if signs is None else backend.as_i8p(signs),
+            backend.as_i32p(indptr), backend.as_i32p(indices), int(n_components), backend.as_f64p(mean.view(np.float64)),
+            None if stderr is None else backend.as_f64p(stderr.view(np.float64))))
+        return mean, stderr
+
     def green_state_moments(self, scale, n_moments, amplitudes, n_components: int = 4) -> np.ndarray:
         """(n_moments, n_states, 4, n_components) complex moments <w_q a|T_n(H/scale)|w_q b> of the states
         `amplitudes` (n_states, n_sites): one complex amplitude per site, the same on every Nambu component

@@ -113,6 +113,10 @@ typedef struct bdg_perf {
     double gemm_ms;        /* bdg_response_map: HIP-event time of its product launches (resp_gemm) */
     double gemm_flops;     /* bdg_response_map: 8 x n_moments^2 x K summed over the chunks of sites and the kernels, K = 4 x
                               padded columns x sites of the chunk complex entries per panel row */
+    int32_t green_probe;   /* bdg_green_probe_blocks: 1 = its steps ran the streamed-block kernel, 2 = the dictionary kernel
+                              (cheb_family / cheb_family_dict with GreenBondTail); 0 = the call was another one.  (The newest
+                              field: with `correlation` it fills the eight bytes before gram_ms, four of which were padding -
+                              the record keeps its size, `correlation` moved by four bytes and no other field moved.) */
     int32_t correlation;   /* bdg_moment_matrix: 1 = the call was this one, 0 = another one */
     double gram_ms;        /* bdg_moment_matrix: HIP-event time of its Gram + reduce launches (corr_gram, corr_reduce) */
     double gram_flops;     /* bdg_moment_matrix: 8 x rows of X x rows of Y x K summed over the Gram launches, K = 4 nb x
@@ -347,6 +351,49 @@ int bdg_green_local_moments(bdg_system* sys, double scale, int32_t n_moments, in
  */
 int bdg_green_bond_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
                           const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* out);
+
+/*
+ * Green's function blocks on a pattern of block pairs by probing: one start vector per colour of sites
+ * and Nambu column where bdg_green_bond_blocks has one per column site and Nambu column.  site_colour[i] < n_colours is
+ * the caller's colour of block row i (negative: the site is no source), signs[s*nb + i] = xi_i = +1 or -1 the sign of
+ * site i in sample s < n_samples (NULL: all +1, n_samples must be 1).  Per sample, for the pattern block k = (j, i)
+ * with c = site_colour[i] >= 0,
+ *   x_s[e][k][a][b] = xi_i * sum_n w[e][n] [T_n(H/scale) r_{c b}][4j + a],   r_{c b} = sum_{i': colour(i') = c} xi_i' e_{4i' + b}
+ * - the block G_ji plus xi_i xi_i' G_ji' of the other sites i' of the colour; a block whose column site has a negative
+ * colour is returned as 0.  mean_out, in the layout of bdg_green_bond_blocks' out, is the mean of x_s over the samples;
+ * stderr_out (NULL allowed, same layout) holds sqrt(sum_s (x_s - mean)^2 / (S (S - 1))) of the real parts in its real
+ * part and of the imaginary parts in its imaginary part, zeros for one sample.  Weights, pattern and n_components as
+ * for bdg_green_bond_blocks; the hole-column rule holds term by term because the signs are real.  A batch of the
+ * one-step width rule holds the vectors of 64 / n_components whole colours or a power of two less (bdg_set_lanes_per_row
+ * fixes the lanes); green_probe_start writes the start vectors, the launches, the pick of moment 0 and the contraction
+ * are those of bdg_green_bond_blocks with the colour of a block's column site where that call has the site's position
+ * (kernels cheb_family / cheb_family_dict with GreenBondTail: one writer per entry, because a pattern row may hold a
+ * colour only once).  After a sample's last contraction green_probe_accumulate folds it into mean and squared deviations
+ * on the device (Welford: delta = x - mean, mean += delta / s, M2 += delta (x - mean); one thread per entry, no atomics;
+ * one sample returns x bit for bit).  The device table covers a range of moments of at most 256 MB
+ * (BODGE_AMD_GREEN_TABLE_BYTES).  Argument errors come before any device call, in this order: counts (n_moments,
+ * n_weights < 1; n_weights above 262140; n_colours < 1; n_samples < 1), scale <= 0, null pointers (signs == NULL with
+ * n_samples > 1 after the others), null handle, a pattern whose indptr does not start at 0 or is not monotone, that has
+ * no block, whose indices leave [0, nb) or are not in canonical order, n_components not 2 or 4, a colour >= n_colours, a
+ * sign that is not +1 or -1, a pattern row that holds two column sites of one colour (the message names the row), slab,
+ * a batch of 2^31 / 16 blocks or more (the table is indexed with 32 bits).  bdg_perf_query reports the call: green_probe
+ * says which kernel form ran, launches = n_samples x colour batches x (n_moments - 1), kernel_ms the recurrence launches,
+ * window_ms the whole.  Ends a Lanczos run or a subspace block on the handle.  Whole matrices only (not slabs).
+ */
+int bdg_green_probe_blocks(bdg_system* sys, double scale, int32_t n_moments, int32_t n_weights, const double* weights,
+                           int32_t n_colours, const int32_t* site_colour, int32_t n_samples, const int8_t* signs,
+                           const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components, double* mean_out,
+                           double* stderr_out);
+
+/*
+ * The argument checks of bdg_green_probe_blocks from "a pattern whose indptr ..." to "two column sites of one colour",
+ * in that order, for a matrix of nb block rows: on the host, without a handle or a device (after nb, n_colours,
+ * n_samples < 1, null pointers and signs == NULL with n_samples > 1).  0 or BDG_EINVAL with the same messages.  For
+ * tests and for callers that want to validate colours and signs before they create a handle; the Python package itself
+ * does not call it, and bdg_green_probe_blocks runs the same function.
+ */
+int bdg_host_probe_check(int64_t nb, int32_t n_colours, const int32_t* site_colour, int32_t n_samples, const int8_t* signs,
+                         const int32_t* pat_indptr, const int32_t* pat_indices, int32_t n_components);
 
 /*
  * Chebyshev moments of the resolvent between extended states, for G(eps) in plane waves, wave packets or orbitals
